@@ -13,7 +13,12 @@ all-reduces and the row-block reduction of the fc6/fc7/fc8 weight gradients
 (all-to-all of the layer inputs + all-gather of dY, exchange.GradShard).
 
 A step = one pass over one batch; inputs are resident in HBM before timing.
-Prints ONE JSON line (rank 0).  --workload vote_roi times configs[1]
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps
+eager steps, writes the last step's outputs when --dump-outputs DIR is given,
+and prints the line; --full adds every secondary measurement (per-op and
+roofline passes, HIP-graph replay timing, other precisions, step distribution,
+CPU baseline, one-GPU reference of an N > 1 run).
+--workload vote_roi times configs[1]
 (hough_voting_gpu + 2x roi_pool forward, B = 1, test mode) instead;
 --workload linemod times configs[4] per rank: LINEMOD C = 16, 4 objects per
 frame, the configs[2] step plus backproject forward + backward (G = 64,
@@ -31,6 +36,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md, chip parameters)
 FP32_MFMA_PEAK_TFS = 157.3   # MI355X f32-input MFMA dense peak (same guide)
 BF16_MFMA_PEAK_TFS = 2500.0  # MI355X bf16 MFMA dense peak (same guide; no sparsity)
+SETTLE_CALLS = 200           # untimed step calls in front of every timed region (measure())
 
 
 def parse(argv=None):
@@ -41,9 +47,20 @@ def parse(argv=None):
     p.add_argument("--workload", choices=["full", "vote_roi", "linemod"], default="full")
     p.add_argument("--batch", type=int, default=0, help="images per rank (default 8 full / 1 vote_roi)")
     p.add_argument("--classes", type=int, default=22)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="beside the timed steps also run the secondary measurements: the per-op and in-step GEMM "
+                        "breakdown passes and the rooflines, the HIP-graph replay timing (the faster of replay and "
+                        "eager launches is then reported), the other GEMM precisions and the no-dropout step, the "
+                        "per-step distribution, the practical HBM peak, the CPU baseline, and for N > 1 the one-GPU "
+                        "reference.  Without it: set up, warm up, time --steps eager steps, print the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / "
+                        "float64; outputs above 2^20 elements as a fixed seeded sample); the inputs and weights are "
+                        "seeded, so two builds run with the same arguments can be compared output for output")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU baseline budget (bounded sample)")
-    p.add_argument("--no-graph", action="store_true", help="time eager launches instead of a HIP graph")
+    p.add_argument("--no-graph", action="store_true",
+                   help="--full: time eager launches only, no HIP-graph replay")
     p.add_argument("--flat-argmax", action="store_true",
                    help="RoI-pool argmax as the reference's int32 flat index instead of uint16 pixel indices (A/B)")
     p.add_argument("--precision", type=int, choices=[0, 1, 2], default=2,
@@ -54,7 +71,7 @@ def parse(argv=None):
     p.add_argument("--prep-on-main", action="store_true",
                    help="dropout masks and ADD row classification on the step's stream (PoseStep side_prep=False)")
     p.add_argument("--no-fp32-leg", "--no-precision-legs", dest="no_legs", action="store_true",
-                   help="skip the secondary steps at the other GEMM precisions reported beside the main line")
+                   help="--full: skip the secondary steps at the other GEMM precisions reported beside the main line")
     p.add_argument("--global-batch", type=int, default=0,
                    help="global batch the vote's index_size = 128 / global_batch is taken from (default: per-rank "
                         "batch x ranks; e.g. 64 runs one rank at configs[3]'s per-rank geometry, index_size 2)")
@@ -70,7 +87,7 @@ def parse(argv=None):
                    help="pipelined, one GPU: do not join the weight-gradient stream at the end of a step; the next "
                         "step waits for it only where it first rewrites what that stream reads")
     p.add_argument("--graph-repeat", type=int, default=1,
-                   help="HIP-graph timing: capture this many times the minimal step group (2 steps pipelined, else 1) "
+                   help="--full, HIP-graph timing: capture this many times the minimal step group (2 steps pipelined, else 1) "
                         "in one replay (the streams are joined once per replay)")
     p.add_argument("--step-priority", choices=["normal", "high"], default="normal",
                    help="run the step's own stream at high HIP stream priority (its side / prefetch streams stay "
@@ -78,7 +95,7 @@ def parse(argv=None):
     p.add_argument("--no-fuse-loss-tail", action="store_true",
                    help="ADD loss row tail and pose-head backward as separate launches (PoseStep fuse_loss_tail=False)")
     p.add_argument("--no-n1-reference", action="store_true",
-                   help="N > 1: skip rank 0's one-GPU run of its own shard at the same geometry")
+                   help="--full, N > 1: skip rank 0's one-GPU run of its own shard at the same geometry")
     return p.parse_args(argv)
 
 
@@ -241,14 +258,16 @@ def main():
                      label=torch.rand((B, H, W, C), generator=g, device=dev),
                      depth=to(fr["depth"]), label3d=torch.rand((B, G_BP, G_BP, G_BP, C), generator=g, device=dev),
                      grad=torch.randn((B, G_BP, G_BP, G_BP, CH_BP), generator=g, device=dev))
+        bp_out = {}  # the last step's back-projection outputs (--dump-outputs)
 
         def run():
             step_run()
             with step._t("backproject_fwd"):
-                bpo.backproject(bp_in["data"], bp_in["label"], bp_in["depth"], inputs["meta"], bp_in["label3d"],
-                                G_BP, 1, 0.02)
+                bp_out["fwd"] = bpo.backproject(bp_in["data"], bp_in["label"], bp_in["depth"], inputs["meta"],
+                                                bp_in["label3d"], G_BP, 1, 0.02)
             with step._t("backproject_bwd"):
-                bpo.backproject_grad(bp_in["data"], bp_in["depth"], inputs["meta"], bp_in["grad"], G_BP, 1, 0.02)
+                bp_out["bwd"] = bpo.backproject_grad(bp_in["data"], bp_in["depth"], inputs["meta"], bp_in["grad"],
+                                                     G_BP, 1, 0.02)
     if not full:  # vote_roi
         hout = {}
         pool = {}
@@ -286,9 +305,9 @@ def main():
     barrier()
 
     # (1) per-op breakdown: eager steps with HIP events around every op on the
-    # stream the kernels run on (feeds the roofline objects)
+    # stream the kernels run on (feeds the roofline objects); --full only
     ops = {}
-    if step is not None:
+    if args.full and step is not None:
         step.timer = {}
         nb = max(3, min(args.steps, 10))
         for _ in range(nb):
@@ -297,7 +316,7 @@ def main():
         for k, evs in step.timer.items():
             ops[k] = sum(a.elapsed_time(b) for a, b in evs) / nb
         step.timer = None
-    else:
+    elif args.full:
         vr_timer["on"] = True
         nb = max(3, min(args.steps, 20))
         for _ in range(nb):
@@ -311,9 +330,9 @@ def main():
     # (1b) in-step GEMM times: eager steps with the stream overlap left on and
     # HIP events around each FC GEMM on the stream it is launched on (the
     # weight gradients run on the side stream beside the data-gradient
-    # chain), i.e. each kernel's duration as it runs in the timed step
+    # chain), i.e. each kernel's duration as it runs in the timed step; --full only
     gemm_in_step = {}
-    if step is not None:
+    if args.full and step is not None:
         step.gemm_timer = {}
         nb = max(3, min(args.steps, 10))
         for _ in range(nb):
@@ -324,17 +343,18 @@ def main():
         step.gemm_timer = None
 
     # (2) timed region: K steps bracketed by a barrier + device sync on both
-    # sides, max over ranks.  On one GPU the step runs both as a HIP-graph
-    # replay (no host launch cost) and as eager launches on the step's two
-    # streams (the weight-gradient branch overlaps the data-gradient chain);
-    # both execute the same kernels on the same data, and the faster is
-    # reported (both times are in the JSON line).  N > 1: eager, with the RCCL
+    # sides, max over ranks, as eager launches on the step's two streams (the
+    # weight-gradient branch overlaps the data-gradient chain).  --full on one
+    # GPU: the step also runs as a HIP-graph replay (no host launch cost)
+    # before that; both execute the same kernels on the same data, and the
+    # faster is reported (both times are in the JSON line; the eager form has
+    # been the faster one in every recorded line).  N > 1: eager, with the RCCL
     # collectives inside the step.
     graph_replay = None
     # pipelined: one replay = two steps (both minibatches; the prefetch stream
     # is joined at the replay's end, as capture requires), so K must be even
     per_replay = (2 if pipelined else 1) * args.graph_repeat
-    if world == 1 and not args.no_graph and args.steps % per_replay == 0:
+    if args.full and world == 1 and not args.no_graph and args.steps % per_replay == 0:
         def run_replay_body():
             for _ in range(per_replay):
                 run()
@@ -357,7 +377,11 @@ def main():
             torch.cuda.synchronize()
 
     def measure(fn, per_call=1):
-        for _ in range(2):
+        # untimed calls first, so the timed steps run at the GPU's running
+        # clocks whatever came before: straight after 5 warm-up steps a 20-step
+        # line read 3-4 % slower than after 200 (1.78-1.80 vs 1.725 ms per
+        # step on one MI355X).  A fixed count: every rank runs the same steps
+        for _ in range(SETTLE_CALLS):
             fn()
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
@@ -381,12 +405,17 @@ def main():
         modes["hipgraph"] = measure(graph_replay, per_replay)
     modes["eager"] = measure(run)
     mode = min(modes, key=modes.get)
+    if args.dump_outputs:  # the state the last timed (eager) step left; nothing has run since
+        torch.cuda.synchronize()  # every stream of the step
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     step_outputs(step, bp_out if linemod else None) if full else
+                     vote_roi_outputs(hout["o"], pool["p5"], pool["p4"]))
     # the same step with the FC GEMMs at the other precisions, eager, reported
     # beside the line as labelled secondary keys: split-bf16 x3 (~2^-16 per
     # product: fp32-class for the 1e-4 quaternion bound, not fp32-faithful) and
     # plain fp32 MFMA
     legs = {}
-    if args.workload == "full" and world == 1 and not args.no_legs:
+    if args.full and args.workload == "full" and world == 1 and not args.no_legs:
         for prec, key, desc in ((1, "bf16x3_step", "split-bf16 x3 MFMA (k_gemm_x3, hi*hi + hi*lo + lo*hi)"),
                                 (0, "fp32_mfma_step", "fp32 MFMA (k_gemm_f32, 32x32x2f32)")):
             if prec == args.precision:
@@ -420,14 +449,16 @@ def main():
     # per-step distribution of the reported mode (after the timed region, which
     # it does not touch): one HIP event pair per step (median and
     # p10 / p90), and the practical HBM peak (device-to-device copy) beside the
-    # spec peak of the roofline
-    dist_steps = distribution(graph_replay if mode == "hipgraph" else run, min(max(args.steps, 100), 200),
-                              per_replay if mode == "hipgraph" else 1,
-                              group=2 if defer_join and mode != "hipgraph" else 1)
-    if defer_join and mode != "hipgraph":
-        dist_steps["grouping"] = "pairs of steps (deferred weight-gradient join), per step"
-    dist_steps["mode"] = mode
-    practical = d2d_gbs(dev)
+    # spec peak of the roofline; --full only
+    dist_steps = practical = None
+    if args.full:
+        dist_steps = distribution(graph_replay if mode == "hipgraph" else run, min(max(args.steps, 100), 200),
+                                  per_replay if mode == "hipgraph" else 1,
+                                  group=2 if defer_join and mode != "hipgraph" else 1)
+        if defer_join and mode != "hipgraph":
+            dist_steps["grouping"] = "pairs of steps (deferred weight-gradient join), per step"
+        dist_steps["mode"] = mode
+        practical = d2d_gbs(dev)
     value = frames / elapsed
     if step is not None:  # pipelined: both minibatches' sets (the last trained and the prefetched one)
         rows_sets = [int(st["hough"]["num_rois"][0].item()) for st in step._sets]
@@ -487,7 +518,7 @@ def main():
     # HBM traffic of the same launches from the committed rocprofv3 FETCH_SIZE /
     # WRITE_SIZE passes (scripts/gpu.sh pmc -> scripts/pmc_traffic.py)
     pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_path) and world == 1 and gB == B:  # the committed passes' shapes
+    if args.full and os.path.exists(pmc_path) and world == 1 and gB == B:  # the committed passes' shapes
         try:
             pmc = json.load(open(pmc_path))
             wl = pmc.get(args.workload, {})
@@ -518,7 +549,7 @@ def main():
     # geometry (same frames, same index_size, no collectives), the per-GPU
     # reference a like-for-like scaling ratio divides by; the other ranks wait
     n1_ref = None
-    if dist is not None and full and not args.no_n1_reference:
+    if args.full and dist is not None and full and not args.no_n1_reference:
         if rank == 0:
             step1 = PoseStep(B, H, W, C, dev, is_train=1, skip_pixels=10, global_batch=gB, batch_base=rank * B,
                              dist=None, precision=args.precision, weights=step.weights, pipeline=pipelined,
@@ -545,13 +576,14 @@ def main():
         dist.barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not linemod:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not linemod:
         cpu = cpu_baseline(fr, full, args.cpu_seconds)
 
     if rank == 0:
-        if True:
-            log(f"timed mode: {mode}; per-op ms/step (eager breakdown pass): " + json.dumps({k: round(v, 4) for k, v in sorted(ops.items(), key=lambda x: -x[1])}))
-            log(f"RoI rows per step (rank 0): {rows_sets}; per rank: {rows_per_rank}")
+        log(f"timed mode: {mode}; RoI rows per step (rank 0): {rows_sets}; per rank: {rows_per_rank}")
+        if args.full:
+            log("per-op ms/step (eager breakdown pass): " +
+                json.dumps({k: round(v, 4) for k, v in sorted(ops.items(), key=lambda x: -x[1])}))
         out = {
             "metric": "frames/sec 640x480x21-class Hough-vote+RoI+ADD-loss, 1/2/4/8 MI355X",
             "value": round(value, 2),
@@ -562,6 +594,7 @@ def main():
                       "roi_rows_per_rank": rows_per_rank},
             "steps": args.steps,
             "warmup": args.warmup,
+            "settle_calls": SETTLE_CALLS,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -596,21 +629,83 @@ def main():
                 "parallelism": (f"image-shard x{world} (RCCL: row-count/loss all-reduce, fc weight-gradient "
                                 f"row blocks via all-to-all + all-gather)") if world > 1 else "single",
             },
-            "roofline": roof,
-            "roofline_vote": roof_vote,
-            "ops_ms_per_step": {k: round(v, 4) for k, v in ops.items()},
-            "gemm_us_in_step": {k: round(v * 1e3, 1) for k, v in gemm_in_step.items()},
             "timing": mode,
             "timing_ms_per_step": {k: round(v / args.steps * 1e3, 4) for k, v in modes.items()},
-            "step_ms_distribution": dist_steps,
-            "hbm_practical_peak": practical,
-            "cpu_baseline": cpu,
-            "n1_same_geometry": n1_ref,
-            **legs,
+            "full": args.full,
         }
+        if args.full:  # the secondary measurements
+            out.update({
+                "roofline": roof,
+                "roofline_vote": roof_vote,
+                "ops_ms_per_step": {k: round(v, 4) for k, v in ops.items()},
+                "gemm_us_in_step": {k: round(v * 1e3, 1) for k, v in gemm_in_step.items()},
+                "step_ms_distribution": dist_steps,
+                "hbm_practical_peak": practical,
+                "cpu_baseline": cpu,
+                "n1_same_geometry": n1_ref,
+                **legs,
+            })
+        if args.dump_outputs:
+            out["outputs_dir"] = args.dump_outputs
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20        # elements kept of an output with more than this many
+DUMP_MAX_BYTES = 64 << 20    # cap on everything one --dump-outputs run writes
+
+
+def step_outputs(step, bp_out=None):
+    """What a caller of PoseStep.step() holds after the call: the loss, the
+    vote's RoI rows, the pose prediction and the loss's bottom_diff (live
+    rows), every weight / bias gradient and both feature-map gradients
+    (linemod: + the back-projection's forward and backward outputs)."""
+    h = step.hough  # the set the last step trained on
+    n = int(h["num_rois"][1].item())
+    out = [("loss", step.loss), ("num_rois", h["num_rois"])]
+    out += [(f"hough_{k}", h[k][:n]) for k in ("box", "pose", "target", "weight", "domain")]
+    out += [("pose_pred", step.pred[:n]), ("loss_diff", step.diff[:n])]
+    out += [(f"grad_{k}", g) for k, g in step.grads.items()]
+    out += [("grad_conv4", step.dconv4), ("grad_conv5", step.dconv5)]
+    if bp_out is not None:
+        out += [(f"backproject_top{i}", t) for i, t in enumerate(bp_out["fwd"])]
+        out += [("backproject_grad", bp_out["bwd"])]
+    return out
+
+
+def vote_roi_outputs(o, p5, p4):
+    """The vote_roi step's outputs: the vote's RoI rows and both pools' (top,
+    argmax) over the live rows."""
+    n = int(o["num_rois"][1].item())
+    out = [("num_rois", o["num_rois"])]
+    out += [(f"hough_{k}", o[k][:n]) for k in ("box", "pose", "target", "weight", "domain")]
+    for name, (top, arg) in (("conv5", p5), ("conv4", p4)):
+        out += [(f"roi_pool_{name}_top", top[:n]), (f"roi_pool_{name}_argmax", arg[:n])]
+    return out
+
+
+def dump_outputs(dirname, named):
+    """Write each (name, device tensor) as dirname/<name>.npy: float32 as it
+    is, every other dtype as float64; a tensor above DUMP_SAMPLE elements as
+    the 1-D sample at DUMP_SAMPLE sorted indices drawn from a fixed seed (a
+    function of its size only, so two runs sample the same elements)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in named:
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(2024).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"wrote {len(named)} outputs ({total / 1e6:.1f} MB) to {dirname}")
 
 
 def distribution(fn, n, per_call=1, group=1):

@@ -22,7 +22,7 @@ export TMPDIR=/tmp
 prof() {  # prof NAME STEPS WARMUP [bench args] (eager launches, one dispatch per kernel)
   local n=$1 s=$2 w=$3; shift 3
   (cd /tmp && timeout -k 10 600 rocprofv3 "${PMC[@]}" --kernel-trace --output-format csv -d $O/$n -o run -- \
-     python3 $R/bench.py --steps $s --warmup $w --no-cpu-baseline --no-fp32-leg "$@" > $O/$n.log 2>&1)
+     python3 $R/bench.py --full --steps $s --warmup $w --no-cpu-baseline --no-fp32-leg "$@" > $O/$n.log 2>&1)
 }
 while [ $# -gt 0 ]; do
   task=$1; shift
@@ -38,8 +38,8 @@ while [ $# -gt 0 ]; do
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 1 ;;
     bench)
-      timeout -k 10 600 python bench.py > $O/bench_full.json 2> $O/bench_full.err || exit 1
-      timeout -k 10 300 python bench.py --workload vote_roi --steps 200 --warmup 20 \
+      timeout -k 10 600 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err || exit 1
+      timeout -k 10 300 python bench.py --full --workload vote_roi --steps 200 --warmup 20 \
         > $O/bench_vr.json 2> $O/bench_vr.err || exit 1 ;;
     prof)
       PMC=(--stats)
@@ -67,7 +67,7 @@ while [ $# -gt 0 ]; do
       for i in 1 2; do
         for v in tree "${vs[@]}"; do
           L=$R/posecnn_amd/libposecnn_hip.so; [ $v = tree ] || L=$R/scratch/$v.so
-          POSECNN_HIP_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --steps 30 2>/dev/null | \
+          POSECNN_HIP_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 30 2>/dev/null | \
             python -c "import json,sys; d=json.load(sys.stdin); print('$v', d['value'], d['timing_ms_per_step'])" \
             >> $O/ab_lib.log || exit 1
         done

@@ -68,6 +68,39 @@ def test_world_size_must_match_gpus():
         b.check_world(b.parse(["--gpus", "1"]), {"WORLD_SIZE": "4"})
 
 
+def test_full_and_dump_flags():
+    """A plain run is lean: --full is off by default and is no prefix of, nor
+    confused with, --workload full; --dump-outputs takes a directory."""
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = b.parse(["--full", "--workload", "vote_roi", "--dump-outputs", "d"])
+    assert a.full is True and a.workload == "vote_roi" and a.dump_outputs == "d"
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float32 stays float32, other dtypes become float64,
+    small outputs keep their shape, a large one is the same fixed sample on
+    every run, and the total stays under the cap."""
+    import numpy as np
+    import torch
+    b = _bench()
+    big = torch.arange(3 * b.DUMP_SAMPLE, dtype=torch.float32).reshape(3, -1)
+    named = [("small", torch.arange(12, dtype=torch.float32).reshape(3, 4)),
+             ("ints", torch.tensor([2 ** 31 - 1, -5], dtype=torch.int32)),
+             ("big", big)]
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), named)
+    small, ints, s0 = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "ints", "big"))
+    assert small.dtype == np.float32 and small.shape == (3, 4)
+    assert ints.dtype == np.float64 and ints.tolist() == [2 ** 31 - 1, -5]
+    assert s0.dtype == np.float32 and s0.shape == (b.DUMP_SAMPLE,)
+    assert np.all(np.diff(s0) >= 0) and s0.max() < big.numel()  # the values are the sampled indices, sorted
+    assert len(np.unique(s0)) > b.DUMP_SAMPLE // 2 and s0.max() > 2 * b.DUMP_SAMPLE  # spread over the whole output
+    np.testing.assert_array_equal(s0, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= b.DUMP_MAX_BYTES
+
+
 def test_launcher_refuses_missing_gpus():
     """Without enough GPUs the launcher stops before starting any rank."""
     import subprocess
