@@ -207,17 +207,6 @@ int pcnn_add_loss_fwd(const float* pred, const float* target, const float* weigh
  * prep by the caller). */
 int pcnn_add_loss_prep(const float* weight, const float* symmetry, int R_cap, const int32_t* num_rois_dev, int C,
                        int P, void* workspace, size_t workspace_bytes, void* stream);
-/* pcnn_add_loss_prep with the model points (C, P, 3): when the environment
- * sets PCNN_ADD_SEARCH=pruned (P <= 4096) it also builds each symmetric
- * class's Morton order in the workspace, which the ADD-S nearest-point search
- * then prunes with (the same bits as the default full O(P^2) scan). */
-/* Byte offset in the loss workspace of the pruned search's diagnostics
- * (what = 0: the Morton orders, C x P int32; 1: int32 [blocks scanned, blocks
- * held] of the last search), -1 when P is past the pruned search's limit. */
-long pcnn_add_loss_ws_offset(int R_cap, int C, int P, int what);
-int pcnn_add_loss_prep_points(const float* weight, const float* symmetry, const float* points, int R_cap,
-                              const int32_t* num_rois_dev, int C, int P, void* workspace, size_t workspace_bytes,
-                              void* stream);
 int pcnn_add_loss_fwd_prepared(const float* pred, const float* target, const float* weight, const float* points,
                                const float* symmetry, int R_cap, const int32_t* num_rois_dev, int C, int P,
                                float margin, int loss_norm_rows, const int32_t* loss_norm_rows_dev, float* loss,

@@ -64,9 +64,6 @@ _SIGS = {
     "pcnn_add_loss_fwd_prepared": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                   c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcnn_add_loss_prep": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "pcnn_add_loss_ws_offset": (ctypes.c_long, [c_int, c_int, c_int, c_int]),
-    "pcnn_add_loss_prep_points": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
-                                          c_size_t, c_void_p]),
     "pcnn_add_loss_fwd_head_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                            c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                            c_void_p, c_void_p, c_void_p]),

@@ -7,6 +7,8 @@ average_distance_loss(pred (R,4C), target, weight, points (C,P,3), symmetry (C),
     -> (loss (1,), bottom_diff (R,4C))   [ADD, or ADD-S for symmetric classes]
 average_distance_loss_grad(bottom_diff, grad, margin) -> grad[0] * bottom_diff
 """
+import warnings
+
 import torch
 
 from .. import _lib
@@ -20,25 +22,19 @@ def average_distance_loss_prep(bottom_weight, bottom_symmetry, num_points, works
     """Row classification of the loss (pcnn_add_loss_prep) into `workspace`
     (uint8, >= workspace_bytes); may run on another stream as soon as the
     weights exist.  Follow with average_distance_loss(..., prepared=True,
-    workspace=workspace) ordered after it.  With the model `points` (C, P, 3)
-    it also orders the symmetric classes' points for the pruned ADD-S search
-    (pcnn_add_loss_prep_points); without them the loss scans in full (the
-    same bits)."""
+    workspace=workspace) ordered after it (the same bits as the unprepared
+    call).  `points` is deprecated and ignored (DeprecationWarning): callers
+    written for the removed pruned ADD-S search passed the model points here;
+    the loss they get is the same, bit for bit."""
+    if points is not None:
+        warnings.warn("average_distance_loss_prep: `points` is ignored (the pruned ADD-S search is removed)",
+                      DeprecationWarning, stacklevel=2)
     _lib.require_gpu(bottom_weight, bottom_symmetry, workspace)
     w = bottom_weight.contiguous().float()
     R, PC = w.shape
-    lib = _lib.load()
-    if points is not None:
-        if points.shape[1] != num_points:
-            raise ValueError("average_distance_loss_prep: points (C, num_points, 3)")
-        rc = lib.pcnn_add_loss_prep_points(_lib.ptr(w), _lib.ptr(bottom_symmetry.contiguous().float()),
-                                           _lib.ptr(points.contiguous().float()), R, _lib.ptr(num_rois), PC // 4,
-                                           int(num_points), _lib.ptr(workspace), workspace.numel(),
-                                           _lib.stream_ptr())
-    else:
-        rc = lib.pcnn_add_loss_prep(_lib.ptr(w), _lib.ptr(bottom_symmetry.contiguous().float()), R,
-                                    _lib.ptr(num_rois), PC // 4, int(num_points), _lib.ptr(workspace),
-                                    workspace.numel(), _lib.stream_ptr())
+    rc = _lib.load().pcnn_add_loss_prep(_lib.ptr(w), _lib.ptr(bottom_symmetry.contiguous().float()), R,
+                                        _lib.ptr(num_rois), PC // 4, int(num_points), _lib.ptr(workspace),
+                                        workspace.numel(), _lib.stream_ptr())
     _lib.check(rc, "average_distance_loss_prep")
 
 
@@ -92,20 +88,6 @@ def average_distance_loss_total(R, num_classes, num_points, workspace, loss, num
     rc = _lib.load().pcnn_add_loss_total(R, _lib.ptr(num_rois), num_classes, num_points, _lib.ptr(workspace),
                                          workspace.numel(), _lib.ptr(loss), _lib.stream_ptr())
     _lib.check(rc, "average_distance_loss_total")
-
-
-def search_diagnostics(workspace, R, num_classes, num_points):
-    """(Morton orders (C, P) int32, [blocks scanned, blocks held]) that the
-    pruned ADD-S search left in `workspace` (None when it is off)."""
-    lib = _lib.load()
-    o_perm = lib.pcnn_add_loss_ws_offset(R, num_classes, num_points, 0)
-    o_stat = lib.pcnn_add_loss_ws_offset(R, num_classes, num_points, 1)
-    if o_perm < 0:
-        return None
-    n = num_classes * num_points * 4
-    perm = workspace[o_perm:o_perm + n].view(torch.int32).view(num_classes, num_points)
-    stat = workspace[o_stat:o_stat + 8].view(torch.int32)
-    return perm, stat
 
 
 def average_distance_loss_grad(bottom_diff, grad, margin=0.01, name=None, num_rois=None, out=None):

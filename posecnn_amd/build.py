@@ -2,6 +2,7 @@
 
 Each source compiles to its own object under build/ (in parallel), then the
 objects link into the shared library."""
+import glob
 import os
 import subprocess
 import sys
@@ -14,8 +15,7 @@ OUT = os.path.join(HERE, "libposecnn_hip.so")
 SOURCES = ["capi.hip", "hough_compact.hip", "hough_vote.hip", "hough_peak.hip", "hough_emit.hip", "roi_pooling.hip",
            "average_distance.hip", "backprojecting.hip", "pose_head.hip", "gemm_x6.hip", "box_nms.hip",
            "label_producer.hip", "icp.hip", "dropout.hip", "pose2d.hip", "gemm_tp.hip"]
-HEADERS = [os.path.join(CSRC, "pcnn_common.h"), os.path.join(CSRC, "hough_common.h"), os.path.join(CSRC, "gemm_common.h"),
-           os.path.join(HERE, "..", "include", "posecnn_hip.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "posecnn_hip.h")]
 # -ffp-contract=off: the parity arithmetic rounds every float op separately
 # (reference semantics restated by oracle/); MFMA kernels are unaffected.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]

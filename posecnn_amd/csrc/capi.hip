@@ -1,7 +1,8 @@
 // C-ABI housekeeping entry points of libposecnn_hip.so (see include/posecnn_hip.h).
 #include "pcnn_common.h"
 
-extern "C" int pcnn_abi_version(void) { return 2; }
+// 3: the two entry points of the pruned ADD-S search are gone
+extern "C" int pcnn_abi_version(void) { return 3; }
 
 extern "C" const char* pcnn_strerror(int code) {
   switch (code) {

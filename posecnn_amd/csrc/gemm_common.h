@@ -81,9 +81,6 @@ __host__ __device__ constexpr int split_bk(int prec) { return prec == 2 ? 16 : 3
 
 // tile edge of the split kernels for a (capacity) shape
 __host__ __device__ __forceinline__ int tile_x3(int M, int N, int K) {
-#ifdef PCNN_FORCE_TILE
-  return PCNN_FORCE_TILE;
-#endif
   return (M <= 128 || N <= 128 || K <= 128) ? 128 : 256;
 }
 
@@ -127,11 +124,7 @@ __host__ __device__ __forceinline__ XPlan x_plan(int Meff, int N, int Keff, int 
   p.Tm = (rows + 31) / 32 * 32;
   p.mode = 0;
   p.S = 1;
-#ifdef PCNN_NOSPLIT
-  if (false) {
-#else
   if (p.tiles > 0 && p.tiles < G / 2) {
-#endif
     int s = G / p.tiles;
     if (s > p.ns / (128 / BK)) s = p.ns / (128 / BK);
     if (s > kMaxSplitX) s = kMaxSplitX;
@@ -262,9 +255,6 @@ __device__ __forceinline__ void x_epilogue(const GemmArgs& g, const XPlan& pl, c
         // here rather than by an in-place reduce pass (keep_in_epilogue)
         if constexpr (T == 128)
           if (!g.drop && g.keep != 1.f) v = v / g.keep;
-#ifdef PCNN_ABL_NOEPI
-        if (v != 1.2345e-30f) continue;
-#endif
         const unsigned co = ok ? cbase + (unsigned)((qrow(i, q) * g.ldc + j * EB) * 4) : kXOob;
         if (g.c_stream)  // non-temporal: the output is far larger than L2 + MALL
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), oc.rs, co, 0, kXNonTemporal);

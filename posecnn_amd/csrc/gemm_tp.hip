@@ -59,11 +59,7 @@ struct Item {
   int t, z, kl, n;
 };
 
-#ifdef PCNN_TP_NOREAD  // timing ablation (wrong results): operands from registers, no LDS fragment reads
-#define TP_FRAG(ptr) (fake)
-#else
 #define TP_FRAG(ptr) (*(const bf16x8*)(ptr))
-#endif
 
 template <bool GEN>
 __global__ void __launch_bounds__(512, 1) k_gemm_tp(TpArgs p) {
@@ -84,10 +80,6 @@ __global__ void __launch_bounds__(512, 1) k_gemm_tp(TpArgs p) {
   const int lane = pcnn::lane_id(), wave = threadIdx.x >> 6;
   const int wm = wave / 4, wn = wave % 4;
   const int r = lane & 31, hsel = lane >> 5;
-#ifdef PCNN_TP_NOREAD
-  bf16x8 fake;
-  for (int e = 0; e < 8; e++) fake[e] = (__bf16)(float)((lane * 7 + e) & 15);
-#endif
   const int kstep = (pl.ns + pl.S - 1) / pl.S;
   auto item_of = [&](int it) {
     Item I;
@@ -168,11 +160,9 @@ __global__ void __launch_bounds__(512, 1) k_gemm_tp(TpArgs p) {
       for (int s = 0; s < I.n; s++, f++) {
         // this wave's pieces of step f landed (step f + 1's may still fly),
         // then every wave's, and every wave is done reading step f - 1's stage
-#ifndef PCNN_TP_NOBAR
         if (issued > f + 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-#endif
         if (l_it < nitems) {  // step f + 2 into the stage step f - 1 used
           issue((f + 2) % kNStage);
           issued++;
@@ -211,9 +201,6 @@ __global__ void __launch_bounds__(512, 1) k_gemm_tp(TpArgs p) {
     else if (amw == 2) kloop(IC<2>{});
     else if (amw == 1) kloop(IC<1>{});
     else kloop(IC<0>{});
-#ifdef PCNN_TP_NOEPI
-    if (acc[0][0][0] == 1234.5f)  // ablation: stores only on an impossible value
-#endif
     x_epilogue<TT, 4>(g, pl, acc, m0, n0, rl, I.z, wm, wn, r, hsel);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may outlive the workgroup

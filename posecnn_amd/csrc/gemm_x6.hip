@@ -134,11 +134,7 @@ __device__ __forceinline__ void x6_store_part(const float (&v)[8], char* pl, int
   }
 }
 
-#ifdef PCNN_X6_NOREAD  // timing ablation (wrong results): fragments from a register, no LDS reads
-#define X6_FRAG(ptr) (fake)
-#else
 #define X6_FRAG(ptr) (*(const bf16x8*)(ptr))
-#endif
 
 template <int T, bool A_T, bool B_T, bool RAGGED, bool A2, bool GEN>
 __global__ void __launch_bounds__(X6Tile<T>::threads, T == 256 ? 1 : 2) k_gemm_x6(GemmArgs g) {
@@ -157,18 +153,10 @@ __global__ void __launch_bounds__(X6Tile<T>::threads, T == 256 ? 1 : 2) k_gemm_x
   // XCD-aware order (as k_gemm_x3): the workgroups of one XCD take consecutive items
   int wg = blockIdx.x;
   if (wg >= active) return;
-#ifndef PCNN_OLD_XCD_MAP
   wg = xcd_remap(wg, active);
-#else
-  if (active % 8 == 0) wg = (wg % 8) * (active / 8) + wg / 8;
-#endif
   const int lane = pcnn::lane_id(), wave = threadIdx.x >> 6;
   const int wm = wave / X::wn, wn = wave % X::wn;
   const int r = lane & 31, hsel = lane >> 5;
-#ifdef PCNN_X6_NOREAD
-  bf16x8 fake;
-  for (int e = 0; e < 8; e++) fake[e] = (__bf16)(float)((lane * 7 + e) & 15);
-#endif
   const long a_el = A_T ? (long)(g.K - 1) * g.lda + g.M : (long)(g.M - 1) * g.lda + g.K;
   const long b_el = B_T ? (long)(g.N - 1) * g.ldb + g.K : (long)(g.K - 1) * g.ldb + g.N;
   const XOp oa = x_op(g.A, g.lda, a_el), oa2 = x_op(g.A2, g.lda, a_el), ob = x_op(g.B, g.ldb, b_el),
@@ -193,15 +181,6 @@ __global__ void __launch_bounds__(X6Tile<T>::threads, T == 256 ? 1 : 2) k_gemm_x
     for (int i = 0; i < AM; i++)
 #pragma unroll
       for (int j = 0; j < 2; j++) acc[i][j] = (f32x16){};
-#ifdef PCNN_X6_M16ABL
-    f32x4 a16[AM][2][4];
-#pragma unroll
-    for (int i = 0; i < AM; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int p = 0; p < 4; p++) a16[i][j][p] = (f32x4){};
-#endif
     if (nsteps > 0) {
       float va[8], vb[8];
       // prologue: stage 0 -> LDS buffer 0, stage 1 -> registers
@@ -289,18 +268,6 @@ __global__ void __launch_bounds__(X6Tile<T>::threads, T == 256 ? 1 : 2) k_gemm_x
 #pragma unroll
                 for (int p = i * 4 / AMW; p < (i + 1) * 4 / AMW; p++) stage_part(p, nxt, kn);
               }
-#ifdef PCNN_X6_M16ABL  // timing ablation (wrong results): the same MFMA work as 16x16x32 instructions
-#pragma unroll
-              for (int j = 0; j < 2; j++) {
-                const bf16x8 fa[6] = {al[c], ah[c], am[c], am[c], ah[c], ah[c]};
-                const bf16x8 fb[6] = {bh[j], bl[j], bm[j], bh[j], bm[j], bh[j]};
-#pragma unroll
-                for (int p = 0; p < 12; p++)
-                  a16[i][j][p & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[p >> 1], fb[p >> 1], a16[i][j][p & 3],
-                                                                             0, 0, 0);
-              }
-              if (false)
-#endif
 #pragma unroll
               for (int j = 0; j < 2; j++) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[c], bh[j], acc[i][j], 0, 0, 0);
@@ -351,16 +318,6 @@ __global__ void __launch_bounds__(X6Tile<T>::threads, T == 256 ? 1 : 2) k_gemm_x
         else kloop_w(IC<3>{});
       }
     }
-#ifdef PCNN_X6_M16ABL
-#pragma unroll
-    for (int i = 0; i < AM; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-#pragma unroll
-          for (int e = 0; e < 4; e++) acc[i][j][4 * p + e] = a16[i][j][p][e];
-#endif
     x_epilogue<T, AM>(g, pl, acc, m0, n0, rl, z, wm, wn, r, hsel);
   };
 

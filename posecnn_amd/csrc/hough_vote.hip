@@ -48,12 +48,8 @@ __device__ __forceinline__ void int_range(float lo, float hi, int x, int cx0, in
 }
 
 __device__ __forceinline__ void add_run(int* row, int a, int b) {
-#ifndef PCNN_ABLATE_ATOMICS
   atomicAdd(&row[a], 1);
   atomicAdd(&row[b + 1], -1);
-#else
-  if (a == 12345678) row[b] = 1;
-#endif
 }
 
 // exact reference predicate over cells [a, b] of one row, runs merged
@@ -151,10 +147,6 @@ __global__ void __launch_bounds__(kVoteThreads) k_hough_vote(int H, int W, int C
     if (k < 0) continue;
     const int ry0 = max(y - k, y0), ry1 = min(y + k, y1 - 1);
     if (ry0 > ry1) continue;
-#ifdef PCNN_ABLATE_ROWS
-    if (ry0 == -12345) diff[0] = 1;
-    continue;
-#endif
     const int bx0 = max(x - k, 0), bx1 = min(x + k, W - 1);
     const float u = q.x, v = q.y;
     if (code & kSlowVoter) {  // pathological direction / threshold: exact predicate everywhere
@@ -171,24 +163,17 @@ __global__ void __launch_bounds__(kVoteThreads) k_hough_vote(int H, int W, int C
       int_range(lo, hi, x, bx0, bx1, oa, ob);
       if (oa > ob) continue;
       int ia = 1, ib = 0;
-#ifdef PCNN_ABLATE_INNER
-      ia = oa; ib = ob;
-      if (false) {
-#else
       if (row_interval(ci1, s.z, ci2, s.w, dy, lo, hi)) {
-#endif
         int_range(lo, hi, x, bx0, bx1, ia, ib);
         ia = max(ia, oa);
         ib = min(ib, ob);
       }
       if (ia <= ib) {
         add_run(row, ia, ib);
-#ifndef PCNN_ABLATE_EXACT
         if (oa < ia) exact_cells(row, oa, ia - 1, r, x, y, u, v, inlier);
         if (ib < ob) exact_cells(row, ib + 1, ob, r, x, y, u, v, inlier);
       } else {
         exact_cells(row, oa, ob, r, x, y, u, v, inlier);
-#endif
       }
     }
   }

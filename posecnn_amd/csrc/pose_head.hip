@@ -285,9 +285,6 @@ __device__ __forceinline__ void x_load_part(const XOp& P, const XOp& P2, int r0,
   // step stay in flight together.  (A2: the summed operand of the generic
   // A + A2 form adds right after its loads.)  Part q = one float4 load.
   const int t = threadIdx.x;
-#ifdef PCNN_ABL_L2
-  k0 &= 127;  // timing ablation: operands stay L2-resident (wrong results)
-#endif
   xf4 x;
   if (KC) {
     const int kq = t & 7;
@@ -339,13 +336,6 @@ __device__ __forceinline__ void x_load(const XOp& P, const XOp& P2, int r0, int 
 // both hi halves, the fp32 value of each hi half by a shift / mask of that
 // pack, one pack-convert for both lo halves.
 __device__ __forceinline__ void x_split2(float a, float b, unsigned& hi, unsigned& lo) {
-#ifdef PCNN_OLDSPLIT
-  const __bf16 ha = (__bf16)a, hb = (__bf16)b;
-  const __bf16 la = (__bf16)(a - (float)ha), lb = (__bf16)(b - (float)hb);
-  hi = (unsigned)__builtin_bit_cast(unsigned short, ha) | ((unsigned)__builtin_bit_cast(unsigned short, hb) << 16);
-  lo = (unsigned)__builtin_bit_cast(unsigned short, la) | ((unsigned)__builtin_bit_cast(unsigned short, lb) << 16);
-  return;
-#endif
   const bf16x2 h = __builtin_convertvector((f32x2){a, b}, bf16x2);
   hi = __builtin_bit_cast(unsigned, h);
   const float ah = __uint_as_float(hi << 16), bh = __uint_as_float(hi & 0xffff0000u);
@@ -408,11 +398,7 @@ __global__ void __launch_bounds__(XTile<T>::threads, T == 256 ? 1 : 2) k_gemm_x3
   // shared operand rows meet in one L2
   int wg = blockIdx.x;
   if (wg >= active) return;
-#ifndef PCNN_OLD_XCD_MAP
   wg = xcd_remap(wg, active);
-#else
-  if (active % 8 == 0) wg = (wg % 8) * (active / 8) + wg / 8;
-#endif
   const int lane = pcnn::lane_id(), wave = threadIdx.x >> 6;
   const int wm = wave / X::wn, wn = wave % X::wn;
   const int r = lane & 31, hsel = lane >> 5;
@@ -499,10 +485,8 @@ __global__ void __launch_bounds__(XTile<T>::threads, T == 256 ? 1 : 2) k_gemm_x3
           char* nxt = xl + ((s + 1) & 1) * kXStage;
           const int kn = kb + (s + 2 < nsteps ? s + 2 : nsteps - 1) * XBK;
           if constexpr (AMW == 0) {
-#ifndef PCNN_ABL_NOSTAGE
 #pragma unroll
             for (int c = 0; c < 8; c++) stage_part(c, nxt, kn);
-#endif
           } else {
 #pragma unroll
             for (int ks = 0; ks < 2; ks++) {
@@ -529,20 +513,15 @@ __global__ void __launch_bounds__(XTile<T>::threads, T == 256 ? 1 : 2) k_gemm_x3
                   acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i & 1], bl[j], acc[i][j], 0, 0, 0);
                   acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i & 1], bh[j], acc[i][j], 0, 0, 0);
                 }
-#ifndef PCNN_ABL_NOSTAGE
                 const int slot = ks * AMW + i;
 #pragma unroll
                 for (int c = slot * 8 / SLOTS; c < (slot + 1) * 8 / SLOTS; c++) stage_part(c, nxt, kn);
-#endif
               }
             }
           }
           __syncthreads();
         }
       };
-#ifdef PCNN_NOAMW
-      kloop(IC<AM>{});
-#else
       if (amw == AM) kloop(IC<AM>{});
       else if (amw == 0) kloop(IC<0>{});
       else if (amw == 1) kloop(IC<1>{});
@@ -550,7 +529,6 @@ __global__ void __launch_bounds__(XTile<T>::threads, T == 256 ? 1 : 2) k_gemm_x3
         if (amw == 2) kloop(IC<2>{});
         else kloop(IC<3>{});
       }
-#endif
     }
 
     x_epilogue<T, AM>(g, pl, acc, m0, n0, rl, z, wm, wn, r, hsel);

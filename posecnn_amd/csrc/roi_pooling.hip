@@ -91,24 +91,15 @@ __device__ __forceinline__ void upd(float v, int idx, float& m, int& a) {
 // cu.cc:469-554), with a run's bins consecutive, so a RoI's feature window is
 // fetched into one L2 and re-read there by its jittered neighbours instead of
 // by all eight XCDs.  Same box, B = 8 bench RoIs: the pool pair 94.6 -> 60 us
-// (PCNN_ROI_XCD=0 is the plain row-fastest order, kept for A/B).
-#ifndef PCNN_ROI_XCD
-#define PCNN_ROI_XCD 1
-#endif
+// against the plain row-fastest order.
 constexpr int kXcds = 8;
 constexpr int kRun = 9;
 __device__ __forceinline__ bool fwd_item(int R, int nbins, int& r, int& bin) {
   const int id = blockIdx.x;
-#if PCNN_ROI_XCD
   const int x = id % kXcds, local = id / kXcds;
   const int lr = local / nbins;
   bin = local % nbins;
   r = ((lr / kRun) * kXcds + x) * kRun + lr % kRun;
-#else
-  const int rows = gridDim.x / nbins;
-  r = id % rows;
-  bin = id / rows;
-#endif
   return r < R;
 }
 // 1-D grid: whole runs on every XCD
@@ -323,9 +314,6 @@ __global__ void __launch_bounds__(1024) k_roi_prep(const float* __restrict__ roi
 // for every masked tile pixel, add the top gradient of each channel whose
 // argmax names that pixel to a register accumulator (cu.cc:219-224) — in
 // list order, so the fp32 sums are bit-equal to the reference's.
-#ifndef PCNN_RBW_XCD
-#define PCNN_RBW_XCD 1
-#endif
 #ifndef PCNN_RBW_NARROW
 #define PCNN_RBW_NARROW 8192
 #endif
@@ -347,14 +335,10 @@ __global__ void __launch_bounds__(64 * kBWaves) k_roi_bwd_ent(const float* __res
   __shared__ int sh_total;
   const int tiles_w = (W + kBTW - 1) / kBTW, tiles_h = (H + kBTH - 1) / kBTH;
   const int nchunk = (C + kBChunk - 1) / kBChunk;
-#if PCNN_RBW_XCD
   // XCD-aware: XCD x takes the contiguous item range [x*ipx, (x+1)*ipx), so
   // neighbouring tiles, which list the same RoI bins, read them through one L2
   const int ipx = (int)((gridDim.x + 7) / 8);
   int id = (int)(blockIdx.x % 8) * ipx + (int)(blockIdx.x / 8);
-#else
-  int id = blockIdx.x;
-#endif
   if (id >= B * tiles_w * tiles_h * nchunk) return;  // grid padded to a multiple of 8
   const int chunk = id % nchunk;
   id /= nchunk;

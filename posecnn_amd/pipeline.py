@@ -293,7 +293,7 @@ class PoseStep:
                 side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(stream or side or torch.cuda.current_stream()):
             adl.average_distance_loss_prep(h["weight"], symmetry, points.shape[1], st["add_ws"],
-                                           num_rois=h["num_rois"][1:2], points=points)
+                                           num_rois=h["num_rois"][1:2])
         st["prepped"] = "side" if side is not None else "stream"
 
     def pool_fwd(self, conv4, conv5, s=None):
