@@ -13,18 +13,19 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libposecnn_hip.so")
 SOURCES = ["capi.hip", "hough_compact.hip", "hough_vote.hip", "hough_peak.hip", "hough_emit.hip", "roi_pooling.hip",
-           "average_distance.hip", "backprojecting.hip", "pose_head.hip", "gemm_x6.hip", "box_nms.hip",
-           "label_producer.hip", "icp.hip", "dropout.hip", "pose2d.hip", "gemm_tp.hip"]
+           "average_distance.hip", "backprojecting.hip", "pose_head.hip", "gemm.hip", "gemm_f32.hip", "gemm_x3.hip",
+           "gemm_x6.hip", "box_nms.hip", "label_producer.hip", "icp.hip", "dropout.hip", "pose2d.hip", "gemm_tp.hip"]
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "posecnn_hip.h")]
 # -ffp-contract=off: the parity arithmetic rounds every float op separately
 # (reference semantics restated by oracle/); MFMA kernels are unaffected.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
-# pose_head: the SLP vectorizer pairs the hi/lo split of two staged floats from
+# The GEMM files: the SLP vectorizer pairs the hi/lo split of two staged floats from
 # different load tuples into v_pk_add_f32, which forces register copies of the
 # freshly loaded tuples at the loop edge -- each behind a vmcnt wait that
-# exposes the full load latency every K step.
-FILE_FLAGS = {"pose_head.hip": ["-fno-slp-vectorize"], "gemm_x6.hip": ["-fno-slp-vectorize"],
-              "gemm_tp.hip": ["-fno-slp-vectorize"]}
+# exposes the full load latency every K step.  (pose_head.hip: built with the
+# flag since its kernels shared a file with the GEMMs.)
+NO_SLP = ["pose_head.hip", "gemm.hip", "gemm_f32.hip", "gemm_x3.hip", "gemm_x6.hip", "gemm_tp.hip"]
+FILE_FLAGS = {src: ["-fno-slp-vectorize"] for src in NO_SLP}
 
 
 def _obj(src):

@@ -1,8 +1,10 @@
-// Shared pieces of the pose-head GEMMs (pose_head.hip: fp32 MFMA and the
-// split-bf16 x3 kernel; gemm_x6.hip: the 3-way split-bf16 x6 kernel): the
-// argument block, the device-side dims, buffer-descriptor operand views, the
-// persistent tile plan and the split-kernel epilogue.
+// Shared pieces of the pose-head GEMMs (gemm.hip: the entry points and the
+// split-K reducer; gemm_f32.hip, gemm_x3.hip, gemm_x6.hip, gemm_tp.hip: the
+// kernels): the argument block, the device-side dims, buffer-descriptor
+// operand views, the split kernels' epilogue, and the launch of a kernel
+// variant.  The shape -> plan arithmetic is in gemm_plan.h.
 #pragma once
+#include "gemm_plan.h"
 #include "pcnn_common.h"
 #include <type_traits>
 
@@ -31,12 +33,12 @@ struct GemmArgs {
   int ldm;
   const int32_t* M_dev;
   const int32_t* K_dev;
-  float* slab;  // split-K partials: [kMaxSplit][M][N] (fp32 path), [S][M][N] (split kernels)
+  float* slab;  // split-K partials: [kF32MaxSplit][M][N] (fp32 path), [S][M][N] (split kernels)
   int prec;     // 0 fp32 MFMA, 1 split-bf16 x3, 2 split-bf16 x6 (selects the plan's K step)
   int tile;     // split kernels: tile edge (256 or 128), chosen on the host
-  int xgrid;    // split kernels: launch grid (the plan depends on it; k_gemm_reduce re-derives the plan)
+  int xgrid;    // launch grid (the split kernels' plan depends on it; k_gemm_reduce re-derives the plan)
   int c_stream; // split kernels: store C non-temporally (outputs far beyond the caches, e.g. the fc6 weight gradient)
-  // dropout (pose_head.hip k_gemm_reduce applies it; the GEMM kernels' own
+  // dropout (gemm.hip k_gemm_reduce applies it; the GEMM kernels' own
   // epilogues never do): C = (v / keep) * drop[m, n] in the forward; with a
   // mask (the relu + dropout backward) C = (mask > 0 ? v : 0) / keep
   const uint8_t* drop;
@@ -58,11 +60,18 @@ __device__ __forceinline__ float drop_epi(float v, const GemmArgs& g, int m, int
   return v;
 }
 
-// Whether the GEMM epilogue of a whole-tile plan already applied 1 / keep
-// (x_epilogue, 128-row tiles, no forward drop mask): then k_gemm_reduce has
-// nothing left to do for S == 1.
+// keep_in_epilogue (gemm_plan.h) of a prepared argument block
 __host__ __device__ __forceinline__ bool keep_in_epilogue(const GemmArgs& g) {
-  return g.prec != 0 && g.tile == 128 && g.drop == nullptr;
+  return keep_in_epilogue(g.prec, g.tile, g.drop);
+}
+
+// bias / relu / relu-backward mask of one output value (the fp32 kernel and
+// k_gemm_reduce; the split kernels' whole-tile form is x_epilogue)
+__device__ __forceinline__ float epilogue(float v, const GemmArgs& g, int m, int n) {
+  if (g.bias) v += g.bias[n];
+  if (g.act == 1) v = v > 0.f ? v : 0.f;
+  if (g.mask && !(g.mask[(size_t)m * g.ldm + n] > 0.f)) v = 0.f;
+  return v;
 }
 
 __device__ __forceinline__ int eff_dim(int full, const int32_t* dev) {
@@ -73,68 +82,6 @@ __device__ __forceinline__ int eff_dim(int full, const int32_t* dev) {
 
 template <int N>
 using IC = std::integral_constant<int, N>;
-
-// K step of a split kernel: 32 (x3: hi / lo planes, 64-B LDS rows) or 16
-// (x6: hi / mid / lo planes, 48-B LDS rows; three planes of a 32-deep step
-// would not fit two LDS stages)
-__host__ __device__ constexpr int split_bk(int prec) { return prec == 2 ? 16 : 32; }
-
-// tile edge of the split kernels for a (capacity) shape
-__host__ __device__ __forceinline__ int tile_x3(int M, int N, int K) {
-  return (M <= 128 || N <= 128 || K <= 128) ? 128 : 256;
-}
-
-// Plan of the split kernels for an effective shape (M and K may live on the
-// device; the host evaluates the same plan for workspace sizing).
-//  - M tiles are balanced: mt = ceil(M / T) tiles of Tm rows each, Tm the
-//    smallest multiple of 32 >= M / mt (M = 405: 224 + 181 rows, not
-//    256 + 149), so the tiles of one N column carry about the same number of
-//    live 32-row accumulator blocks; rows past a tile's end are padding whose
-//    MFMAs the K loop skips.  The tiles of a column run side by side on one
-//    XCD, share their B panel through L2 and finish together (fc6 dX, 196
-//    tiles in one round: 318 -> 295 us).
-//  - Tile mode: whole tiles dealt round-robin.
-//  - Split-K (fewer than G/2 tiles, long K): S K slices per tile, partial
-//    slabs reduced in slice order by k_gemm_reduce (the forward shapes); a
-//    slice keeps at least 128 of K.
-//  Measured and dropped: stream-K over the tiles of a column (K ranges cut
-//  evenly over workgroup pairs, partial tiles fixed up in fixed order by the
-//  last segment to finish): fc6 dX 295 -> 343 us — the slab round trip and
-//  the per-segment fix-up cost more than the balance gains.
-#ifndef PCNN_MAX_SPLIT_X
-#define PCNN_MAX_SPLIT_X 32
-#endif
-constexpr int kMaxSplitX = PCNN_MAX_SPLIT_X;  // split-K slices
-struct XPlan {
-  int mt, nt, ns, Tm, tiles, mode, S;
-  bool m_fast;  // tile order: the dimension with fewer tiles runs fastest (its
-                // neighbours share the other operand's tile in L2)
-  __host__ __device__ int mi_of(int t) const { return m_fast ? t % mt : t / nt; }
-  __host__ __device__ int ni_of(int t) const { return m_fast ? t / mt : t % nt; }
-};
-
-__host__ __device__ __forceinline__ XPlan x_plan(int Meff, int N, int Keff, int T, int G, int BK) {
-  XPlan p;
-  p.mt = (Meff + T - 1) / T;
-  p.nt = (N + T - 1) / T;
-  p.ns = (Keff + BK - 1) / BK;
-  p.tiles = p.mt * p.nt;
-  p.m_fast = p.mt <= p.nt;
-  const int rows = p.mt ? (Meff + p.mt - 1) / p.mt : 0;
-  p.Tm = (rows + 31) / 32 * 32;
-  p.mode = 0;
-  p.S = 1;
-  if (p.tiles > 0 && p.tiles < G / 2) {
-    int s = G / p.tiles;
-    if (s > p.ns / (128 / BK)) s = p.ns / (128 / BK);
-    if (s > kMaxSplitX) s = kMaxSplitX;
-    if (s > 1) {
-      p.mode = 1;
-      p.S = s;
-    }
-  }
-  return p;
-}
 
 // XCD-aware item order: the dispatcher deals workgroup b to XCD b % 8, so a
 // bijective remap gives each XCD one contiguous run of items (neighbouring
@@ -265,10 +212,77 @@ __device__ __forceinline__ void x_epilogue(const GemmArgs& g, const XPlan& pl, c
   }
 }
 
-// Launch of the x6 kernel (gemm_x6.hip) for a prepared argument block.
-void launch_gemm_x6(const GemmArgs& g, int grid, bool a_trans, bool b_trans, bool ragged, bool a2, bool gen,
-                    hipStream_t st);
-// LDS bytes of one x6 workgroup at tile edge T
-int gemm_x6_lds(int T);
+// ---------------------------------------------------------------------------
+// Host side: the launch of a kernel variant.
+
+// Raises Kernel's dynamic-LDS limit to `bytes`, once per device (the
+// attribute is per device: one flag per device ordinal).
+template <auto Kernel>
+inline void allow_dynamic_lds(int bytes) {
+  static bool attr_set[pcnn::kMaxDevices] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= pcnn::kMaxDevices || !attr_set[dev]) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (dev >= 0 && dev < pcnn::kMaxDevices) attr_set[dev] = true;
+  }
+}
+
+// Which instantiation of a split kernel family runs: the operand layouts, the
+// element-wise edge loads, the summed A + A2 operand, and the kernel form of
+// the launch plan.  g.tile and g.xgrid carry the plan's tile edge and grid.
+struct SplitVariant {
+  bool a_trans, b_trans;
+  bool ragged;  // a float4 of a staging load may straddle an operand edge
+  bool a2;      // A + A2
+  bool gen;     // LaunchPlan::gen
+};
+
+// The runtime -> compile-time switch over the variants of a kernel family.
+// Family (X3Family in gemm_x3.hip, X6Family in gemm_x6.hip) names the kernel
+// template, its tile geometry (threads, lds) and whether the kernel takes the
+// op's completion event.  Per layout / edge / A2 combination three kernels
+// exist: tile 128 (always the general form), tile 256 general (split-K
+// capable: device-side M, or a static shape that splits) and tile 256 lean
+// (whole tiles only: the static-M tile-mode shapes, e.g. fc6 / fc7 dW).
+template <class Family>
+struct SplitLaunch {
+  template <int T, bool AT, bool BT, bool RG, bool S2, bool GN>
+  static void one(const GemmArgs& g, hipStream_t st) {
+    using Tile = typename Family::template Tile<T>;
+    constexpr auto kernel = Family::template kernel<T, AT, BT, RG, S2, GN>();
+    allow_dynamic_lds<kernel>(Tile::lds);
+    if constexpr (Family::takes_done_event) pcnn::launch_last(kernel, dim3(g.xgrid), dim3(Tile::threads), Tile::lds, st, g);
+    else hipLaunchKernelGGL(kernel, dim3(g.xgrid), dim3(Tile::threads), Tile::lds, st, g);
+  }
+  template <bool AT, bool BT, bool RG, bool S2>
+  static void form(const GemmArgs& g, const SplitVariant& v, hipStream_t st) {
+    if (g.tile != 256) one<128, AT, BT, RG, S2, true>(g, st);
+    else if (v.gen) one<256, AT, BT, RG, S2, true>(g, st);
+    else one<256, AT, BT, RG, S2, false>(g, st);
+  }
+  template <bool RG, bool S2>
+  static void layout(const GemmArgs& g, const SplitVariant& v, hipStream_t st) {
+    if (!v.a_trans && !v.b_trans) form<false, false, RG, S2>(g, v, st);
+    else if (!v.a_trans && v.b_trans) form<false, true, RG, S2>(g, v, st);
+    else if (v.a_trans && !v.b_trans) form<true, false, RG, S2>(g, v, st);
+    else form<true, true, RG, S2>(g, v, st);
+  }
+  static void launch(const GemmArgs& g, const SplitVariant& v, hipStream_t st) {
+    if (!v.ragged && !v.a2) layout<false, false>(g, v, st);
+    else if (!v.ragged) layout<false, true>(g, v, st);
+    else if (!v.a2) layout<true, false>(g, v, st);
+    else layout<true, true>(g, v, st);
+  }
+};
+
+// The kernels' launches for a prepared argument block (grid g.xgrid).  Only
+// the x6 kernel takes the op's completion event (pcnn::launch_last): after an
+// fp32 or x3 GEMM without a reduce the event stays pending.
+void launch_gemm_f32(const GemmArgs& g, bool a_trans, bool b_trans, hipStream_t st);  // gemm_f32.hip
+void launch_gemm_x3(const GemmArgs& g, const SplitVariant& v, hipStream_t st);        // gemm_x3.hip
+void launch_gemm_x6(const GemmArgs& g, const SplitVariant& v, hipStream_t st);        // gemm_x6.hip
+// k_gemm_reduce (gemm.hip): split-K slabs + epilogue, dropout
+void launch_gemm_reduce(const GemmArgs& g, hipStream_t st);
 
 }  // namespace pcnn_gk

@@ -238,22 +238,11 @@ __global__ void __launch_bounds__(256) k_split_tp(const float* __restrict__ src,
 
 template <bool GEN>
 void launch_tp(const TpArgs& a, int grid, hipStream_t st) {
-  static bool attr_set[pcnn::kMaxDevices] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= pcnn::kMaxDevices || !attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)k_gemm_tp<GEN>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    if (dev >= 0 && dev < pcnn::kMaxDevices) attr_set[dev] = true;
-  }
+  allow_dynamic_lds<&k_gemm_tp<GEN>>(kLds);
   hipLaunchKernelGGL(k_gemm_tp<GEN>, dim3(grid), dim3(512), kLds, st, a);
 }
 
 }  // namespace
-
-namespace pcnn_gk {
-// k_gemm_reduce (pose_head.hip): split-K slabs + epilogue, dropout
-void launch_gemm_reduce(const GemmArgs& g, hipStream_t st);
-}
 
 extern "C" size_t pcnn_tp_bytes(int rows, int K) {
   if (rows <= 0 || K <= 0) return 256;
@@ -283,30 +272,15 @@ extern "C" int pcnn_gemm_tp(int M, int N, int K, const void* A_tp, const void* B
   PCNN_REQUIRE((long)M * ldc < (1l << 29) && (!mask || (long)M * ldm < (1l << 29)));
   if (M == 0) return PCNN_OK;
   if (workspace_bytes < pcnn_gemm_workspace_size(M, N, K, M_dev != nullptr, 2) || !workspace) return PCNN_ECAPACITY;
+  // as pcnn_gemm at precision 2, at this kernel's one tile edge
+  const LaunchPlan plan = plan_launch(M, N, K, M_dev != nullptr, 2, TT);
   GemmArgs g{M, N, K, nullptr, nullptr, 0, nullptr, 0, Cm, ldc, bias, act, mask, ldm, M_dev, K_dev,
-             (float*)workspace, 2, TT, 0, 0, drop, ldd, keep_prob};
-  const int max_grid = 256;
-  long grid = max_grid;
-  bool gen = true, may_split = true;
-  if (!M_dev) {  // as pcnn_gemm: static M -> fewest workgroups that keep the rounds
-    const XPlan pl = x_plan(M, N, K, TT, max_grid, 16);
-    may_split = pl.mode == 1;
-    if (pl.mode == 0) {
-      gen = false;
-      const long items = pl.tiles;
-      const long rounds = (items + max_grid - 1) / max_grid;
-      grid = (items + rounds - 1) / rounds;
-      grid = (grid + 7) / 8 * 8;
-      if (grid > max_grid) grid = max_grid;
-    }
-  }
-  g.xgrid = (int)grid;
-  g.c_stream = (long)M * N * 4 > (256l << 20);
+             (float*)workspace, 2, TT, plan.grid, plan.c_stream, drop, ldd, keep_prob};
   TpArgs a{g, (const char*)A_tp, (const char*)B_tp, (K + 15) / 16, (K + 15) / 16, (M + 31) / 32, (N + 31) / 32};
   hipStream_t st = (hipStream_t)stream;
-  if (gen) launch_tp<true>(a, (int)grid, st);
-  else launch_tp<false>(a, (int)grid, st);
-  if (may_split || drop || keep_prob != 1.f) launch_gemm_reduce(g, st);
+  if (plan.gen) launch_tp<true>(a, plan.grid, st);
+  else launch_tp<false>(a, plan.grid, st);
+  if (reduce_follows(plan, 2, drop, keep_prob)) launch_gemm_reduce(g, st);
   PCNN_CHECK_LAUNCH();
   return PCNN_OK;
 }

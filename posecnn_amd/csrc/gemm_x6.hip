@@ -1,5 +1,5 @@
 // Three-way split-bf16 ("bf16x6") GEMM for the pose-head FC layers — the
-// fp32-faithful MFMA path (precision 2) of pcnn_gemm (pose_head.hip).
+// fp32-faithful MFMA path (precision 2) of pcnn_gemm (gemm.hip).
 //
 // The reference runs fc6 / fc7 / fc8 as fp32 tf.matmul
 // (lib/networks/network.py:393-423, wired at vgg16_convs.py:186-197).  Every
@@ -15,7 +15,7 @@
 // reference's fp32 GEMM, at 6/16 of the fp32-MFMA cost (bf16 MFMA issues 16x
 // the flops of v_mfma_f32_32x32x2_f32 per cycle).
 //
-// Structure as k_gemm_x3 (pose_head.hip): a persistent tile loop over a
+// Structure as k_gemm_x3 (gemm_x3.hip): a persistent tile loop over a
 // device-side plan (balanced M tiles, split-K slabs for the forward shapes,
 // XCD-aware item order), fp32 operands split while staging into LDS (the
 // weights stay fp32 in HBM), two LDS stages with the loads of step s+2 in
@@ -329,48 +329,21 @@ __global__ void __launch_bounds__(X6Tile<T>::threads, T == 256 ? 1 : 2) k_gemm_x
   }
 }
 
-template <int T, bool AT, bool BT, bool RG, bool S2, bool GN>
-void launch_one(const GemmArgs& g, int grid, hipStream_t st) {
-  // the attribute is per device: one flag per device ordinal
-  static bool attr_set[pcnn::kMaxDevices] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= pcnn::kMaxDevices || !attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)k_gemm_x6<T, AT, BT, RG, S2, GN>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, X6Tile<T>::lds);
-    if (dev >= 0 && dev < pcnn::kMaxDevices) attr_set[dev] = true;
-  }
+struct X6Family {
+  template <int T>
+  using Tile = X6Tile<T>;
   // the op's last launch when no reduce follows (gemm_impl holds the completion event back otherwise)
-  pcnn::launch_last(k_gemm_x6<T, AT, BT, RG, S2, GN>, dim3(grid), dim3(X6Tile<T>::threads), X6Tile<T>::lds, st, g);
-}
-
-template <bool AT, bool BT, bool RG, bool S2>
-void launch_tile(const GemmArgs& g, int grid, bool gen, hipStream_t st) {
-  if (g.tile != 256) launch_one<128, AT, BT, RG, S2, true>(g, grid, st);
-  else if (gen) launch_one<256, AT, BT, RG, S2, true>(g, grid, st);
-  else launch_one<256, AT, BT, RG, S2, false>(g, grid, st);  // whole tiles only (static-M tile-mode shapes)
-}
-
-template <bool RG, bool S2>
-void launch_layout(const GemmArgs& g, int grid, bool a_trans, bool b_trans, bool gen, hipStream_t st) {
-  if (!a_trans && !b_trans) launch_tile<false, false, RG, S2>(g, grid, gen, st);
-  else if (!a_trans && b_trans) launch_tile<false, true, RG, S2>(g, grid, gen, st);
-  else if (a_trans && !b_trans) launch_tile<true, false, RG, S2>(g, grid, gen, st);
-  else launch_tile<true, true, RG, S2>(g, grid, gen, st);
-}
+  static constexpr bool takes_done_event = true;
+  template <int T, bool AT, bool BT, bool RG, bool S2, bool GN>
+  static constexpr auto kernel() {
+    return &k_gemm_x6<T, AT, BT, RG, S2, GN>;
+  }
+};
 
 }  // namespace
 
 namespace pcnn_gk {
 
-void launch_gemm_x6(const GemmArgs& g, int grid, bool a_trans, bool b_trans, bool ragged, bool a2, bool gen,
-                    hipStream_t st) {
-  if (!ragged && !a2) launch_layout<false, false>(g, grid, a_trans, b_trans, gen, st);
-  else if (!ragged) launch_layout<false, true>(g, grid, a_trans, b_trans, gen, st);
-  else if (!a2) launch_layout<true, false>(g, grid, a_trans, b_trans, gen, st);
-  else launch_layout<true, true>(g, grid, a_trans, b_trans, gen, st);
-}
-
-int gemm_x6_lds(int T) { return T == 256 ? X6Tile<256>::lds : X6Tile<128>::lds; }
+void launch_gemm_x6(const GemmArgs& g, const SplitVariant& v, hipStream_t st) { SplitLaunch<X6Family>::launch(g, v, st); }
 
 }  // namespace pcnn_gk

@@ -1,7 +1,7 @@
 // Philox4x32-10 (Salmon et al., SC'11; Random123 constants) and TF's
 // Uint32ToFloat keep test of tf.nn.dropout, shared by the keep-mask kernel
 // (dropout.hip) and the GEMM reduce epilogue that draws the masks in place
-// (pose_head.hip k_gemm_reduce, drop_gen).  Counter of element quad e of a
+// (gemm.hip k_gemm_reduce, drop_gen).  Counter of element quad e of a
 // dense (rows, cols) mask: (e lo, e hi, stream id, step); key = the seed.
 #pragma once
 #include <stdint.h>

@@ -600,9 +600,6 @@ class PoseStep:
         elif side is not None:
             main.wait_stream(side)
 
-    def _gemm(self, A, B, C, **kw):
-        return ph.gemm(A, B, C, precision=self.prec, **kw)
-
     def _g(self, name, A, B, C, **kw):
         """One FC GEMM at the step's precision, bracketed by HIP events on the
         stream it is launched on when gemm_timer is set."""

@@ -70,3 +70,23 @@ def test_forward_shapes_bit_identical(hip, M, N, K, mdev):
     ph.gemm_tp(At, Bt, C, rows, N, K, bias=b, act=1, M_dev=Md, drop=drop, keep_prob=0.5)
     m = mdev or M
     assert torch.equal(C[:m], ref[:m])
+
+
+def test_device_rows_without_split_bit_identical(hip):
+    """Device-side rows on a shape whose plan cannot split for any M (at M = 1:
+    2 tiles, 12 K steps -> split cap 1), so no reduce follows the GEMM kernel:
+    bit-identical to the staged x6 kernel, rows past M_dev untouched."""
+    cap, m, N, K = 320, 300, 512, 192
+    g = torch.Generator(device=D).manual_seed(cap + N)
+    A = torch.randn((cap, K), generator=g, device=D)
+    W = torch.randn((K, N), generator=g, device=D) * 0.03
+    Md = torch.tensor([m], dtype=torch.int32, device=D)
+    ref = torch.full((cap, N), 7.0, device=D)
+    ph.gemm(A, W, ref, M_dev=Md, precision=2)
+    At = _tp(A, cap, K, K, 1, rows_dev=Md)
+    Bt = _tp(W, N, K, 1, N)
+    C = torch.full((cap, N), 7.0, device=D)
+    ph.gemm_tp(At, Bt, C, cap, N, K, M_dev=Md)
+    assert torch.equal(C[:m], ref[:m])
+    assert not torch.equal(C[:m], torch.full((m, N), 7.0, device=D))
+    assert torch.all(C[m:] == 7.0) and torch.all(ref[m:] == 7.0)
