@@ -581,6 +581,48 @@ int pcnn_pose_energy_batch(const float* live, int n_live, const int32_t* label, 
                            const int32_t* pose_live, const int32_t* pose_pv, float* energy, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Mesh rasteriser: the rendered maps the refinement ops above take as inputs,
+ * i.e. the role of the reference's OpenGL pass (synthesize.cpp:2103-2139 with
+ * lib/kinect_fusion/shaders canonicalVerts.* and vertsAndNorms.*).  K problems,
+ * one mesh and one pose each, no texture, colour or lighting.
+ *  packed mesh set (M meshes): vertices / normals (V_total,3) f32 model frame,
+ *    faces (F_total,3) int32 vertex indices LOCAL to their mesh, vert_offset /
+ *    face_offset (M+1) int32 row ranges of each mesh; F_max >= the largest
+ *    mesh's face count.
+ *  per problem: mesh_index (K) int32, class_id (K) int32, poses (K,7)
+ *    (quaternion normalised here).  A mesh_index outside [0, M), or offsets
+ *    that do not fit (V_total, F_total, F_max), render nothing for that problem.
+ *  fx, fy, px, py: pixel (x, y) samples u = x, v = y, u = fx X / Z + px;
+ *    0 < znear <= zfar: a triangle with a vertex at Z < znear is dropped whole
+ *    (no near-plane clipping), a fragment with Z > zfar is discarded.
+ *  outputs, every pixel written (the caller never clears them):
+ *    pred_vertices (K,H,W,4) camera-frame position of the nearest surface
+ *      point, perspective-correct, w = 1; all 0 off the model
+ *    pred_normals (K,H,W,4) interpolated R n / |R n| (not renormalised), w = 0;
+ *      all 0 off the model
+ *    vertmap (K,H,W,3) interpolated model-frame position, class_id added to x
+ *      (synthesize.cpp:267-274); NaN off the model (glClearColor(nan), :2113)
+ *    depth (K,H,W) f32 camera Z, 0 off the model (optional, may be NULL)
+ *    tri_id (K,H,W) int32 winning face within its mesh, -1 off the model
+ *      (optional, may be NULL)
+ *    pred_vertices, pred_normals and the workspace are 16-byte aligned.
+ *  Coverage is exact (vertices snapped to 1/256 px, int64 edge functions, a
+ *  tie rule that gives a shared edge to one triangle), values are float32
+ *  from the unsnapped vertices, the nearest Z wins and an equal Z goes to the
+ *  lower face index: bitwise reproducible, alone or in a batch (rules at the
+ *  top of csrc/render.hip).  The z-buffer is cleared inside the op.
+ *  PCNN_EINVAL: a NULL required pointer, K, H, W, M, V_total or F_max <= 0,
+ *  K > 65535, znear <= 0; PCNN_ECAPACITY: a short workspace.
+ * ------------------------------------------------------------------------- */
+size_t pcnn_render_workspace_size(int K, int H, int W, int V_total, int F_max);
+int pcnn_render_meshes(const float* vertices, const float* normals, const int32_t* faces, const int32_t* vert_offset,
+                       const int32_t* face_offset, int M, int V_total, int F_total, int F_max,
+                       const int32_t* mesh_index, const int32_t* class_id, const float* poses, int K, int H, int W,
+                       float fx, float fy, float px, float py, float znear, float zfar, float* pred_vertices,
+                       float* pred_normals, float* vertmap, float* depth, int32_t* tri_id, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,11 @@ _SIGS = {
                                        c_void_p]),
     "pcnn_pose_energy": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcnn_render_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "pcnn_render_meshes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float,
+                                   c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -2,7 +2,8 @@
 #include "pcnn_common.h"
 
 // 3: the two entry points of the pruned ADD-S search are gone
-extern "C" int pcnn_abi_version(void) { return 3; }
+// 4: the mesh rasteriser (pcnn_render_workspace_size, pcnn_render_meshes)
+extern "C" int pcnn_abi_version(void) { return 4; }
 
 extern "C" const char* pcnn_strerror(int code) {
   switch (code) {

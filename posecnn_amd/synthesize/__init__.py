@@ -1,0 +1,1 @@
+from .render import Mesh, MeshRenderer, load_obj  # noqa: F401
