@@ -623,6 +623,65 @@ int pcnn_render_meshes(const float* vertices, const float* normals, const int32_
                        float* pred_normals, float* vertmap, float* depth, int32_t* tri_id, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Scene renderer: the ground truth of synthetic training frames, i.e. the role
+ * of Synthesizer::render (synthesize.cpp:345-609), of the label / visibility
+ * steps of the render worker (tools/train_net.py:209-230) and of
+ * _generate_vertex_targets (gt_synthesize_layer/minibatch.py:517-575).  S
+ * scenes, K object instances in all, each scene depth-tested across its
+ * instances; no texture, colour or lighting.
+ *  packed mesh set, mesh_index / class_id / poses (K): as pcnn_render_meshes.
+ *  scene_offset (S+1) int32 on the device: scene s holds the instance rows
+ *    [scene_offset[s], scene_offset[s+1]) (a CSR; valid ranges are meant to be
+ *    disjoint, a row named by two valid scenes is drawn in the lower-numbered
+ *    one).  Checked on the device: an empty range, a decreasing one, one that
+ *    leaves [0, K] or one of more than 256 rows renders an all-background
+ *    scene.  An instance with an invalid mesh slot draws nothing.
+ *  Visibility: per scene pixel the nearest Z wins; an equal Z goes to the
+ *    lower rank (the instance's position inside its scene), then to the lower
+ *    face (one 64-bit atomicMin of (Z bits << 32) | (rank << 24) | face, so
+ *    F_max <= 2^24).  Coverage, culling and values are pcnn_render_meshes's: a
+ *    scene of one instance gives that op's bits for the instance.
+ *  outputs, every element written (the caller never clears them):
+ *    label (S,H,W) int32 the winner's class_id, 0 off the models
+ *    depth (S,H,W) f32 camera Z, 0 off the models
+ *    vertmap (S,H,W,3) f32 model coordinates, class_id added to x; NaN off
+ *    vertex3 (S,H,W,3) f32 class-compact vote target of the winning instance
+ *      (the layout pcnn_hough_voting_compact reads), 0 off the models:
+ *      c = (fx (tx / tz) + px, fy (ty / tz) + py) in f32 (synthesize.cpp:558-562);
+ *      channels 0, 1 = (c - (x, y)) / (|c - (x, y)| + 1e-10), difference, norm
+ *      and quotient in double, rounded to f32 (minibatch.py:556-567); channel
+ *      2 = (float)log((double)tz) (:568).  Each pixel uses its own instance's
+ *      centre: the reference's target when a class occurs once per scene.
+ *    inst_id (S,H,W) int32 the winning instance's row in [0, K), -1 off the
+ *      models (optional, may be NULL)
+ *    visible (K) int32 pixels each instance won (train_net.py:222-230), an
+ *      integer sum, zeroed inside the op
+ *    centers (K,2) f32 the c above (8-byte aligned)
+ *  The workspace is 16-byte aligned.  Nothing is allocated or read back; the
+ *  op runs on `stream` and can be captured in a HIP graph.
+ *  PCNN_EINVAL: a NULL required pointer, S, K, H, W, M, V_total or F_max <= 0,
+ *  K > 65535, F_max > 2^24, znear <= 0, misalignment; PCNN_ECAPACITY: a short
+ *  workspace.
+ *
+ * pcnn_vertex_targets_expand: the compact target back into the reference's
+ * blobs.  label (B,H,W) int32, vertex3 (B,H,W,3) -> vertex_targets and
+ * vertex_weights (B,H,W,3C), 16-byte aligned: a pixel with label l in [1, C)
+ * gets vertex3 at channels 3l..3l+2 and w_inside (VERTEX_W_INSIDE,
+ * lib/fcn/config.py:64) at the same channels of the weights; everything else
+ * is 0 (minibatch.py:253-254, 566-574).  Every element is written.
+ * ------------------------------------------------------------------------- */
+size_t pcnn_render_scenes_workspace_size(int S, int K, int H, int W, int V_total, int F_max);
+int pcnn_render_scenes(const float* vertices, const float* normals, const int32_t* faces, const int32_t* vert_offset,
+                       const int32_t* face_offset, int M, int V_total, int F_total, int F_max,
+                       const int32_t* mesh_index, const int32_t* class_id, const float* poses, int K,
+                       const int32_t* scene_offset, int S, int H, int W, float fx, float fy, float px, float py,
+                       float znear, float zfar, int32_t* label, float* depth, float* vertmap, float* vertex3,
+                       int32_t* inst_id, int32_t* visible, float* centers, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int pcnn_vertex_targets_expand(const int32_t* label, const float* vertex3, int B, int H, int W, int C, float w_inside,
+                               float* vertex_targets, float* vertex_weights, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

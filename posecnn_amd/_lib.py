@@ -147,6 +147,13 @@ _SIGS = {
                                    c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float,
                                    c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    "pcnn_render_scenes_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "pcnn_render_scenes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float,
+                                   c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcnn_vertex_targets_expand": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                           c_void_p, c_void_p]),
 }
 
 

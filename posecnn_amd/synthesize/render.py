@@ -9,8 +9,9 @@ MeshRenderer(meshes, H, W, camera, ...)    solve_icp's `render`: __call__(obj, p
                                            and render_many(objs, poses) ->
                                            (vertmap, pred_vertices, pred_normals)
 
-No texture, colour or lighting, one object per image; the geometry rules are
-at the top of csrc/render.hip and in DESIGN.md.
+No texture, colour or lighting, one object per image (scene.py renders
+several into one image); the geometry rules are at the top of csrc/render.hip
+and in DESIGN.md.
 """
 import numpy as np
 import torch
@@ -89,16 +90,11 @@ def load_obj(path):
     return Mesh(np.asarray(pos, np.float32), np.asarray(faces, np.int32), normals)
 
 
-class MeshRenderer:
-    """Renders meshes (dict obj_id -> Mesh) at H x W through camera = (fx, fy,
-    px, py); the meshes are packed onto the device once.  Plugs into solve_icp
-    as `render`: render_many(objs, poses (K,7)) -> (vertmap (K,H,W,3),
-    pred_vertices (K,H,W,4), pred_normals (K,H,W,4)), fresh tensors per call;
-    __call__(obj, pose) renders one pose ((H,W,.) maps).  return_depth /
-    return_tri_id append depth (K,H,W) float32 / tri_id (K,H,W) int32.  poses
-    may be numpy or a device tensor (no host sync either way); obj ids are
-    host integers, the class written into vertmap's x.  An object id without a
-    mesh raises KeyError."""
+class PackedMeshes:
+    """The view (H x W, camera = (fx, fy, px, py), znear, zfar) and the mesh
+    set (dict obj_id -> Mesh) packed onto the device once, in the layout the
+    C ABI takes: what MeshRenderer and SceneRenderer share.  slot[obj_id] is
+    the mesh's position in the set (the ABI's mesh_index)."""
 
     def __init__(self, meshes, H, W, camera, znear=0.25, zfar=6.0, device="cuda"):
         self.H, self.W = int(H), int(W)
@@ -107,7 +103,7 @@ class MeshRenderer:
         self.device = torch.device(device)
         _lib.require_gpu()
         if not meshes:
-            raise ValueError("MeshRenderer: no meshes")
+            raise ValueError(f"{type(self).__name__}: no meshes")
         self.slot = {int(o): i for i, o in enumerate(meshes)}
         ms = list(meshes.values())
         voff = np.concatenate([[0], np.cumsum([len(m.vertices) for m in ms])]).astype(np.int32)
@@ -119,6 +115,23 @@ class MeshRenderer:
         self.normals = dev(np.concatenate([m.normals for m in ms]))
         self.faces = dev(np.concatenate([m.faces for m in ms]))
         self.vert_offset, self.face_offset = dev(voff), dev(foff)
+
+    def mesh_args(self):
+        """The packed mesh set as the leading arguments of the C-ABI calls."""
+        return (_lib.ptr(self.vertices), _lib.ptr(self.normals), _lib.ptr(self.faces), _lib.ptr(self.vert_offset),
+                _lib.ptr(self.face_offset), self.M, self.V_total, self.F_total, self.F_max)
+
+
+class MeshRenderer(PackedMeshes):
+    """Renders meshes (dict obj_id -> Mesh) at H x W through camera = (fx, fy,
+    px, py); the meshes are packed onto the device once.  Plugs into solve_icp
+    as `render`: render_many(objs, poses (K,7)) -> (vertmap (K,H,W,3),
+    pred_vertices (K,H,W,4), pred_normals (K,H,W,4)), fresh tensors per call;
+    __call__(obj, pose) renders one pose ((H,W,.) maps).  return_depth /
+    return_tri_id append depth (K,H,W) float32 / tri_id (K,H,W) int32.  poses
+    may be numpy or a device tensor (no host sync either way); obj ids are
+    host integers, the class written into vertmap's x.  An object id without a
+    mesh raises KeyError."""
 
     def render_many(self, objs, poses, return_depth=False, return_tri_id=False, stream=None):
         objs = [int(o) for o in objs]
@@ -168,9 +181,7 @@ class MeshRenderer:
             workspace = _lib.workspace(lib.pcnn_render_workspace_size(K, H, W, self.V_total, self.F_max), self.device,
                                        "render", stream)
         fx, fy, px, py = self.camera
-        rc = lib.pcnn_render_meshes(_lib.ptr(self.vertices), _lib.ptr(self.normals), _lib.ptr(self.faces),
-                                    _lib.ptr(self.vert_offset), _lib.ptr(self.face_offset), self.M, self.V_total,
-                                    self.F_total, self.F_max, _lib.ptr(mesh_index), _lib.ptr(class_id),
+        rc = lib.pcnn_render_meshes(*self.mesh_args(), _lib.ptr(mesh_index), _lib.ptr(class_id),
                                     _lib.ptr(poses), K, H, W, fx, fy, px, py, self.znear, self.zfar,
                                     _lib.ptr(pred_vertices), _lib.ptr(pred_normals), _lib.ptr(vertmap),
                                     _lib.ptr(depth), _lib.ptr(tri_id), _lib.ptr(workspace), workspace.numel(),
