@@ -191,8 +191,25 @@ int pcnn_roi_pool_bwd_px(const float* top_diff, const uint16_t* argmax_px, int B
  *  loss_norm_rows: when > 0, the normaliser R of (d - m)/(2 R P) and of the
  *       gradient (an image-sharded run passes the global row count so that the
  *       per-rank losses sum to the single-device loss); <= 0 uses the local R.
+ *  Symmetric classes (ADD-S): each (row, 256-point chunk) item finds its
+ *       nearest GT-rotated points with a bf16 MFMA filter and an exact fp32
+ *       re-check of the few candidates inside a proved window (the same picks
+ *       and the same bits as the exact scan).  An item with a
+ *       non-finite point, with every point zero or with a squared norm outside
+ *       [2^-40, 2^40] takes the exact scan, and so does every item when P >
+ *       2816 or the device's LDS cannot hold both candidate images.  The
+ *       environment variable PCNN_ADD_SEARCH=scan, read at each launch, forces
+ *       the exact scan everywhere (a test / A-B knob).
+ *  Workspace: pcnn_add_loss_workspace_size grew by one 256-byte slot for three
+ *       int32 search counters at byte offset pcnn_add_loss_stats_offset: the
+ *       symmetric items searched by the filter, those searched by the scan,
+ *       and the filter items' passing (query, block of 32 candidates, half)
+ *       triples (16 exact evaluations each; the int32 sum holds for
+ *       R_cap x chunks up to 47 000 in the worst case).  The row classification
+ *       (pcnn_add_loss_fwd, pcnn_add_loss_prep) zeroes them; the per-point sums add.
  * ------------------------------------------------------------------------- */
 size_t pcnn_add_loss_workspace_size(int R_cap, int C, int P);
+size_t pcnn_add_loss_stats_offset(int R_cap, int C, int P);
 
 int pcnn_add_loss_fwd(const float* pred, const float* target, const float* weight, const float* points,
                       const float* symmetry, int R_cap, const int32_t* num_rois_dev, int C, int P, float margin,

@@ -18,6 +18,17 @@ def workspace_bytes(R, num_classes, num_points):
     return _lib.load().pcnn_add_loss_workspace_size(R, num_classes, num_points)
 
 
+def search_stats(workspace, R, num_classes, num_points):
+    """The ADD-S search counters the last loss on `workspace` left there (a
+    device read): symmetric (row, chunk) items searched by the MFMA filter,
+    items searched by the exact scan (out of the filter's range, or
+    PCNN_ADD_SEARCH=scan), the filter items' passing (query, 32-candidate
+    block, half) triples and their exact evaluations (16 per triple)."""
+    off = _lib.load().pcnn_add_loss_stats_offset(R, num_classes, num_points)
+    f, s, t = workspace[off:off + 12].cpu().view(torch.int32).tolist()
+    return {"filter_items": f, "scan_items": s, "triples": t, "exact_evals": 16 * t}
+
+
 def average_distance_loss_prep(bottom_weight, bottom_symmetry, num_points, workspace, num_rois=None, points=None):
     """Row classification of the loss (pcnn_add_loss_prep) into `workspace`
     (uint8, >= workspace_bytes); may run on another stream as soon as the

@@ -2,7 +2,9 @@
 Hough targets/weights, 22 classes, random predictions normalised as the
 step's l2_normalize does: a unit quaternion on the row's class) with HIP
 events, `--repeats` times over, and check that every repeat gives the same bits.
-    python scripts/add_bench.py [--iters 20] [--repeats 3] [--near]"""
+    python scripts/add_bench.py [--iters 20] [--repeats 3] [--near]
+PCNN_ADD_SEARCH=scan in the environment times the exact scan instead of the
+MFMA filter; the search counters of the last call are printed either way."""
 import argparse
 import os
 import sys
@@ -58,3 +60,15 @@ for _ in range(a.repeats):
     print(f"rows {int(nr.item())} add_fwd {e0.elapsed_time(e1) / a.iters * 1e3:9.1f} us "
           f"loss {float(loss.item()).hex()} diff sha {dig}", flush=True)
 assert len(res) == 1, "repeats differ"
+# the ADD-S search of the last call: items by path, exact evaluations, and the
+# passing (query, 32-candidate block, half) triples per query point
+st = adl.search_stats(ws, R, C, pts.shape[1])
+live = int(nr.item())
+cls = (o["weight"][:live, 0::4] > 0).float().argmax(1)
+has = (o["weight"][:live, 0::4] > 0).any(1)
+nsym = int((has & (sym[cls] > 0)).sum().item())
+queries = max(1, nsym * pts.shape[1])
+print(f"search {os.environ.get('PCNN_ADD_SEARCH', 'filter')}: symmetric rows {nsym}, filter items "
+      f"{st['filter_items']}, scan items {st['scan_items']}, exact evaluations {st['exact_evals']} "
+      f"({st['exact_evals'] / queries:.2f} per query, {st['exact_evals'] / 16 / queries:.2f} passing block halves "
+      f"per query)", flush=True)
