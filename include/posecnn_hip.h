@@ -699,6 +699,80 @@ int pcnn_render_scenes(const float* vertices, const float* normals, const int32_
 int pcnn_vertex_targets_expand(const int32_t* label, const float* vertex3, int B, int H, int W, int C, float w_inside,
                                float* vertex_targets, float* vertex_weights, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Segmentation and vertex-regression losses, forward and backward: loss_cls
+ * and loss_vertex of the training objective (lib/fcn/train.py:489-515).
+ * Common to the four ops: float32 per-element arithmetic with every op rounded
+ * separately, loss sums in double, reductions in a fixed order without
+ * floating-point atomics (two runs give the same bits); `loss` (1) is always
+ * written and every element of every requested output is written; optional
+ * outputs may be NULL; float maps and the workspace are 16-byte aligned; the
+ * ops run on `stream`, allocate nothing, read nothing back and can be captured
+ * in a HIP graph.  grad_scale multiplies the gradient only (the incoming
+ * d loss).  PCNN_EINVAL: a NULL required pointer, a non-positive dimension, an
+ * element count >= 2^31, threshold <= 0, sigma <= 0, misalignment;
+ * PCNN_ECAPACITY: a short workspace.  The *_workspace_size queries return 0
+ * for dimensions the op rejects.
+ *
+ * pcnn_seg_loss: the segmentation head (vgg16_convs.py:140-149,
+ * network.py:475-506, train.py:455-465) from score (B,H,W,C) f32 and gt_label
+ * (B,H,W) int32.  Per pixel: m = max_c score_c, d_c = score_c - m,
+ * e_c = expf(d_c), s = e_0 + e_1 + ... in class order;
+ *    log_prob (B,H,W,C)         d_c - logf(s)
+ *    prob_normalized (B,H,W,C)  e_c / s
+ *    label_2d (B,H,W) int32     first maximum of prob_normalized (pcnn_argmax_2d's rule)
+ *    gt_label_weight (B,H,W,C)  pcnn_hard_label_fwd of (prob_normalized, gt_label, threshold)
+ *    loss = (float)(S / (n + 1e-10)): n the pixels with a non-zero weight row
+ *      (an integer count), S the double sum of -log_prob[gt] over them
+ *    d_score (B,H,W,C)          (prob_normalized_c - [c == gt]) * inv on those
+ *      pixels, 0 elsewhere, inv = grad_scale / ((float)n + 1e-10f): Hardlabel's
+ *      gradient is zero, so the denominator is a constant of the graph.
+ * A gt outside [-1, C) gives a zero weight row.  The workspace keeps (m, s)
+ * per pixel (8 B/px) for the gradient pass.  NaN or infinite scores are
+ * outside the numerical contract (no out-of-bounds access follows).
+ *
+ * pcnn_cross_entropy: loss_cross_entropy_single_frame (train.py:455-465) on
+ * scores and labels, both (n_pix, C): loss = (float)(sum(-(labels * scores)) /
+ * (sum(labels) + 1e-10)), the product in f32, both sums in double;
+ * d_scores (n_pix, C) = -labels * inv, inv = grad_scale / ((float)sum(labels) + 1e-10f).
+ *
+ * pcnn_vertex_loss: smooth_l1_loss_vertex (train.py:565-574) on n elements of
+ * vertex_pred, vertex_targets and vertex_weights.  With c_inv = 1/sigma^2,
+ * c_half = sigma^2/2, c_off = 0.5/sigma^2, c_s2 = sigma^2 computed in double
+ * and rounded to f32: diff = w * (pred - tgt), a = |diff|, near = a < c_inv,
+ * in = near ? (diff * diff) * c_half : a - c_off;
+ *    loss = (float)(sum(in) / (Wsum + 1e-10)), Wsum = sum(w), both in double
+ *    d_pred (n) = (w * (near ? diff * c_s2 : sign(diff))) * inv, sign(0) = 0,
+ *      inv = grad_scale / ((float)Wsum + 1e-10f)
+ * The caller multiplies by VERTEX_W (config.py:63).
+ *
+ * pcnn_vertex_loss_compact: the same loss on the blob pair that
+ * pcnn_vertex_targets_expand(label, vertex3, w_inside) would have written,
+ * without forming it: a pixel with label l in [1, C) contributes its three
+ * channels with weight w_inside, Wsum = (double)w_inside * 3 * count.
+ *    label (B,H,W) int32, vertex3 (B,H,W,3) (pcnn_render_scenes's layout)
+ *    vertex_pred (B,H,W,pred_ch): pred_ch = 3C reads channels 3l..3l+2,
+ *      pred_ch = 3 is pcnn_vertex_pred_compact evaluated at `label`
+ *    d_pred (B,H,W,d_ch), d_ch = 3 or 3C; with 3C every element is written,
+ *      zeros included.  vertex_pred and d_pred are 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+size_t pcnn_seg_loss_workspace_size(int B, int H, int W, int C);
+int pcnn_seg_loss(const float* score, const int32_t* gt_label, int B, int H, int W, int C, float threshold,
+                  float grad_scale, float* log_prob, float* prob_normalized, int32_t* label_2d,
+                  float* gt_label_weight, float* d_score, float* loss, void* workspace, size_t workspace_bytes,
+                  void* stream);
+size_t pcnn_cross_entropy_workspace_size(int n_pix, int C);
+int pcnn_cross_entropy(const float* scores, const float* labels, int n_pix, int C, float grad_scale, float* d_scores,
+                       float* loss, void* workspace, size_t workspace_bytes, void* stream);
+size_t pcnn_vertex_loss_workspace_size(long n);
+int pcnn_vertex_loss(const float* vertex_pred, const float* vertex_targets, const float* vertex_weights, long n,
+                     float sigma, float grad_scale, float* d_pred, float* loss, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t pcnn_vertex_loss_compact_workspace_size(int B, int H, int W, int C);
+int pcnn_vertex_loss_compact(const int32_t* label, const float* vertex3, const float* vertex_pred, int pred_ch, int B,
+                             int H, int W, int C, float w_inside, float sigma, float grad_scale, float* d_pred,
+                             int d_ch, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,18 @@ _SIGS = {
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcnn_vertex_targets_expand": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                            c_void_p, c_void_p]),
+    "pcnn_seg_loss_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcnn_seg_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcnn_cross_entropy_workspace_size": (c_size_t, [c_int, c_int]),
+    "pcnn_cross_entropy": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
+    "pcnn_vertex_loss_workspace_size": (c_size_t, [ctypes.c_long]),
+    "pcnn_vertex_loss": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_float, c_float, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "pcnn_vertex_loss_compact_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcnn_vertex_loss_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                         c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -203,8 +215,21 @@ def require_gpu(*tensors):
             raise ValueError("posecnn_amd ops take device tensors (got a CPU tensor)")
 
 
+class _TensorPtr(ctypes.c_void_p):
+    __slots__ = ("tensor",)
+
+
 def ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+    """Device pointer of `t` as a ctypes argument.  The pointer object keeps
+    its tensor alive: ptr(a temporary) stays valid until the call that takes
+    it has returned (the launch is then ordered on the stream before any
+    reuse of the block), instead of naming a block the caching allocator may
+    already have handed to the next temporary of the same argument list."""
+    if t is None:
+        return None
+    p = _TensorPtr(t.data_ptr())
+    p.tensor = t
+    return p
 
 
 def stream_ptr(stream=None):

@@ -3,7 +3,9 @@
 
 // 3: the two entry points of the pruned ADD-S search are gone
 // 4: the mesh rasteriser (pcnn_render_workspace_size, pcnn_render_meshes)
-extern "C" int pcnn_abi_version(void) { return 4; }
+// 5: the segmentation and vertex losses (pcnn_seg_loss, pcnn_cross_entropy, pcnn_vertex_loss,
+//    pcnn_vertex_loss_compact and their workspace queries)
+extern "C" int pcnn_abi_version(void) { return 5; }
 
 extern "C" const char* pcnn_strerror(int code) {
   switch (code) {

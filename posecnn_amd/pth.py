@@ -12,6 +12,13 @@ its call sites:
         -> pooled (N, C, PH, PW)          rois: [batch, x1, y1, x2, y2]
     AverageDistanceLoss(num_classes, margin)(pred, target, weight, points, symmetry)
         -> loss (1,)
+
+The two dense-map terms of the objective (lib/fcn/train.py:489-515), which the
+reference builds from TF ops, as modules over posecnn_amd.losses:
+
+    SegmentationLoss(threshold)(score_NHWC, gt_label_2d) -> (loss, label_2d)
+    VertexLoss(sigma=1.0, w_inside=10.0)(vertex_pred, vertex_targets, vertex_weights) -> loss
+                                        (vertex_pred, label, vertex3)                 -> loss
 """
 import torch
 from torch import nn
@@ -19,6 +26,7 @@ from torch import nn
 from .hough_voting_gpu_layer import hough_voting_gpu_op as hv
 from .roi_pooling_layer import roi_pooling_op as rp
 from .average_distance_loss import average_distance_loss_op as adl
+from . import losses
 
 
 class HoughVoting(nn.Module):
@@ -71,6 +79,85 @@ class _RoIPooling(nn.Module):
             raise ValueError("rois must be (N, 5): [batch, x1, y1, x2, y2]")
         return _RoIPoolingFn.apply(features.contiguous().float(), rois.contiguous().float(), self.pooled_height,
                                    self.pooled_width, self.spatial_scale)
+
+
+class _SegmentationLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, score, gt_label_2d, threshold):
+        loss, out = losses.seg_loss(score, gt_label_2d, threshold, want=("label_2d",))
+        ctx.save_for_backward(score, gt_label_2d)
+        ctx.threshold = threshold
+        ctx.mark_non_differentiable(out["label_2d"])
+        return loss, out["label_2d"]
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_label):
+        score, gt_label_2d = ctx.saved_tensors
+        # the incoming gradient goes in as the op's grad_scale (a host scalar: one read-back here)
+        _, out = losses.seg_loss(score, gt_label_2d, ctx.threshold, want=("d_score",), grad_scale=float(grad_loss))
+        return out["d_score"].to(score.dtype), None, None
+
+
+class SegmentationLoss(nn.Module):
+    """loss_cls of the segmentation head: (score (B,H,W,C), gt_label_2d (B,H,W))
+    -> (loss, label_2d)."""
+
+    def __init__(self, threshold=1.0):
+        super().__init__()
+        if float(threshold) <= 0:
+            raise ValueError(f"Need threshold > 0, got {threshold}")
+        self.threshold = float(threshold)
+
+    def forward(self, score, gt_label_2d):
+        return _SegmentationLossFn.apply(score, gt_label_2d, self.threshold)
+
+
+class _VertexLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vertex_pred, a, b, compact, num_classes, sigma, w_inside):
+        ctx.save_for_backward(vertex_pred, a, b)
+        ctx.params = (compact, num_classes, sigma, w_inside)
+        if compact:
+            return losses.vertex_loss_compact(vertex_pred, a, b, num_classes, w_inside, sigma)
+        return losses.smooth_l1_loss_vertex(vertex_pred, a, b, sigma)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        vertex_pred, a, b = ctx.saved_tensors
+        compact, num_classes, sigma, w_inside = ctx.params
+        g = float(grad_loss)  # as _SegmentationLossFn.backward
+        if compact:
+            _, d = losses.vertex_loss_compact(vertex_pred, a, b, num_classes, w_inside, sigma, want_grad=True,
+                                              dense_grad=vertex_pred.shape[3] != 3, grad_scale=g)
+        else:
+            _, d = losses.smooth_l1_loss_vertex(vertex_pred, a, b, sigma, want_grad=True, grad_scale=g)
+        return d.to(vertex_pred.dtype), None, None, None, None, None, None
+
+
+class VertexLoss(nn.Module):
+    """loss_vertex before the VERTEX_W factor.  forward(vertex_pred,
+    vertex_targets, vertex_weights) takes the reference's blob pair;
+    forward(vertex_pred, label, vertex3) takes the scene renderer's compact
+    ground truth (label (B,H,W) integer, vertex3 (B,H,W,3)) with weight
+    w_inside on the labelled channels.  A 3-channel vertex_pred (the compact
+    producer's output) needs num_classes."""
+
+    def __init__(self, sigma=1.0, w_inside=10.0, num_classes=None):
+        super().__init__()
+        if float(sigma) <= 0:
+            raise ValueError(f"Need sigma > 0, got {sigma}")
+        self.sigma = float(sigma)
+        self.w_inside = float(w_inside)
+        self.num_classes = None if num_classes is None else int(num_classes)
+
+    def forward(self, vertex_pred, a, b):
+        compact = a.dim() == 3 and not a.dtype.is_floating_point
+        C = self.num_classes
+        if compact and C is None:
+            if vertex_pred.dim() != 4 or vertex_pred.shape[3] == 3:
+                raise ValueError("a 3-channel vertex_pred needs VertexLoss(num_classes=...)")
+            C = vertex_pred.shape[3] // 3
+        return _VertexLossFn.apply(vertex_pred, a, b, compact, C, self.sigma, self.w_inside)
 
 
 class AverageDistanceLoss(nn.Module):
