@@ -167,6 +167,17 @@ int pcnn_roi_pool_fwd_pair_px(const float* data_a, int Ha, int Wa, float scale_a
 
 size_t pcnn_roi_pool_bwd_workspace_size(int B, int R_cap);
 
+/* Which kernel pcnn_roi_pool_bwd (px 0) / pcnn_roi_pool_bwd_px (px 1) runs for
+ * a shape, given 8-B aligned buffers (misaligned ones take the generic kernel):
+ * 0 = generic per-pixel kernel, 1 = entry-list kernel on 1x4-pixel tiles,
+ * 2 = entry-list kernel on 2x4-pixel tiles, negative = the call is rejected
+ * (invalid arguments, or a pixel-index argmax on a shape the entry-list kernel
+ * does not take).  The entry list has room for 49 bins per RoI: NHWC,
+ * all-channel, even-C shapes with pooled_h * pooled_w <= 49 run it, larger
+ * pooled sizes the generic kernel.  Answers on a host without a GPU. */
+int pcnn_roi_pool_bwd_form(int B, int H, int W, int C, int layout, int pool_channel, int pooled_h, int pooled_w,
+                           int R_cap, int px);
+
 int pcnn_roi_pool_bwd(const float* top_diff, const int32_t* argmax, int B, int H, int W, int C, int layout,
                       const float* rois, int R_cap, int roi_stride, int batch_base, const int32_t* num_rois_dev,
                       float spatial_scale, int pooled_h, int pooled_w, int pool_channel, float* bottom_diff,

@@ -54,6 +54,7 @@ _SIGS = {
                                           c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                           c_void_p, c_void_p, c_void_p]),
     "pcnn_roi_pool_bwd_workspace_size": (c_size_t, [c_int, c_int]),
+    "pcnn_roi_pool_bwd_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "pcnn_roi_pool_bwd_px": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                      c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcnn_roi_pool_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,

@@ -17,6 +17,7 @@
 // each entry once and accumulates the argmax-matching top gradients per tile
 // pixel in registers — the fp32 sums are bit-equal to the reference kernel's.
 #include "pcnn_common.h"
+#include "roi_plan.h"
 #include <math.h>
 #include <cfloat>
 
@@ -314,13 +315,12 @@ __global__ void __launch_bounds__(1024) k_roi_prep(const float* __restrict__ roi
 // for every masked tile pixel, add the top gradient of each channel whose
 // argmax names that pixel to a register accumulator (cu.cc:219-224) — in
 // list order, so the fp32 sums are bit-equal to the reference's.
-#ifndef PCNN_RBW_NARROW
-#define PCNN_RBW_NARROW 8192
-#endif
-constexpr int kBWaves = 1;  // one wave per workgroup: a tile's channel chunks land on different CUs
-constexpr int kBChunk = 128 * kBWaves;  // channels per workgroup
-constexpr int kBGroup = 16;             // RoIs expanded per list round (<= 16 * 49 entries)
-constexpr int kBCap = kBGroup * 49;
+// The list holds kBGroup RoIs of at most 49 bins each (kBCap, roi_plan.h): the
+// dispatch sends larger pooled sizes to the generic kernel.
+using pcnn_roi::kBWaves;
+using pcnn_roi::kBChunk;
+using pcnn_roi::kBGroup;
+using pcnn_roi::kBCap;
 constexpr int kBBatch = 8;              // entries per fetch (two fetches in flight per wave)
 
 template <int kBTH, int kBTW, bool PX>
@@ -627,6 +627,11 @@ extern "C" size_t pcnn_roi_pool_bwd_workspace_size(int B, int R_cap) {
          pcnn::align_up((size_t)(R_cap > 0 ? R_cap : 1) * 8 * sizeof(int32_t), 256) + 256;
 }
 
+extern "C" int pcnn_roi_pool_bwd_form(int B, int H, int W, int C, int layout, int pool_channel, int pooled_h,
+                                      int pooled_w, int R_cap, int px) {
+  return pcnn_roi::bwd_plan(B, H, W, C, layout, pool_channel, pooled_h, pooled_w, R_cap, px).form;
+}
+
 static int roi_pool_bwd(const float* top_diff, const void* argmax, bool px, int B, int H, int W, int C, int layout,
                         const float* rois, int R_cap, int roi_stride, int batch_base, const int32_t* num_rois_dev,
                         float spatial_scale, int pooled_h, int pooled_w, int pool_channel, float* bottom_diff,
@@ -636,6 +641,15 @@ static int roi_pool_bwd(const float* top_diff, const void* argmax, bool px, int 
   PCNN_REQUIRE(roi_stride >= 6 || (roi_stride == 5 && !pool_channel));
   PCNN_REQUIRE((long)H * W * C < (1l << 31));
   if (workspace_bytes < pcnn_roi_pool_bwd_workspace_size(B, R_cap)) return PCNN_ECAPACITY;
+  // the form for the shape (roi_plan.h); the entry-list kernel also needs
+  // top_diff readable as b64 and bottom_diff writable as float2 in both forms;
+  // only the argmax (uint16 pixel indices in the px form) may be 4-byte aligned
+  const pcnn_roi::BwdPlan plan =
+      pcnn_roi::bwd_plan(B, H, W, C, layout, pool_channel, pooled_h, pooled_w, R_cap, px ? 1 : 0);
+  const bool aligned =
+      (((uintptr_t)top_diff | (uintptr_t)bottom_diff) & 7) == 0 && ((uintptr_t)argmax & (px ? 3 : 7)) == 0;
+  const bool vec = plan.form != pcnn_roi::kBwdGeneric && aligned;
+  PCNN_REQUIRE(plan.form != pcnn_roi::kBwdRejected && (!px || vec));  // pixel-index argmax: the entry-list kernel only
   hipStream_t st = (hipStream_t)stream;
   pcnn::Carve cv(workspace);
   int32_t* lo = cv.take<int32_t>(B);
@@ -643,32 +657,18 @@ static int roi_pool_bwd(const float* top_diff, const void* argmax, bool px, int 
   int32_t* geo = cv.take<int32_t>((size_t)(R_cap > 0 ? R_cap : 1) * 8);
   hipLaunchKernelGGL(k_roi_prep, dim3(1), dim3(1024), 0, st, rois, R_cap, roi_stride, batch_base, num_rois_dev,
                      B, spatial_scale, pooled_h, pooled_w, geo, lo, hi);
-  // tile shape: 2x4 pixels, or 1x4 when 2x4 tiles would leave the chip short
-  // of workgroups (conv5_3 at 30x40: 4800 -> 9600 workgroups, measured
-  // 64 -> 50 us; conv4_3 at 60x80 keeps 2x4: 77 vs 88 us for 1x4)
-  const int nchunk = (C + kBChunk - 1) / kBChunk;
-  const long wg24 = (long)B * ((H + 1) / 2) * ((W + 3) / 4) * nchunk;
-  const bool narrow = wg24 < PCNN_RBW_NARROW;
-#ifndef PCNN_RBW_TH
-#define PCNN_RBW_TH 2
-#endif
-  const int tbh = narrow ? 1 : PCNN_RBW_TH, tbw = 4;
-  const bool vec = layout == 0 && !pool_channel && C % 2 == 0 && pooled_h * tbh <= 32 && pooled_w * tbw <= 32 &&
-                   (long)H * W * C < (1l << 30) && (long)R_cap * pooled_h * pooled_w * C < (1l << 29) &&
-                   // top_diff is read as b64 and bottom_diff written as float2 in both forms;
-                   // only the argmax (uint16 pixel indices in the px form) may be 4-byte aligned
-                   (((uintptr_t)top_diff | (uintptr_t)bottom_diff) & 7) == 0 && ((uintptr_t)argmax & (px ? 3 : 7)) == 0;
-  PCNN_REQUIRE(!px || (vec && (long)H * W < 0xFFFF));  // pixel-index argmax: the entry-list kernel only
   if (vec) {
+    constexpr int tbw = pcnn_roi::kBTileW;
+    const int tbh = plan.tbh, nchunk = (C + kBChunk - 1) / kBChunk;
     const int tiles = ((H + tbh - 1) / tbh) * ((W + tbw - 1) / tbw);
     const unsigned nwg = (unsigned)((B * tiles * nchunk + 7) / 8 * 8);
 #define PCNN_RBW(TH, PXV)                                                                                  \
-  pcnn::launch_last(k_roi_bwd_ent<TH, 4, PXV>, dim3(nwg), dim3(64 * kBWaves), 0, st, top_diff, argmax, B, H, W, C, \
+  pcnn::launch_last(k_roi_bwd_ent<TH, tbw, PXV>, dim3(nwg), dim3(64 * kBWaves), 0, st, top_diff, argmax, B, H, W, C, \
                     geo, lo, hi, pooled_h, pooled_w, bottom_diff)
-    if (narrow) {
+    if (tbh == 1) {
       if (px) PCNN_RBW(1, true); else PCNN_RBW(1, false);
     } else {
-      if (px) PCNN_RBW(PCNN_RBW_TH, true); else PCNN_RBW(PCNN_RBW_TH, false);
+      if (px) PCNN_RBW(2, true); else PCNN_RBW(2, false);
     }
 #undef PCNN_RBW
   } else {

@@ -40,6 +40,8 @@ def roi_pool(bottom_data, bottom_rois, pooled_height, pooled_width, spatial_scal
     else:
         top, arg = out
     lib = _lib.load()
+    if R == 0:  # nothing to pool; a zero-row tensor has no pointer for the library's argument check
+        return top, arg
     fn = lib.pcnn_roi_pool_fwd_accumulate if accumulate else lib.pcnn_roi_pool_fwd
     rc = fn(_lib.ptr(data), B, H, W, C, layout, _lib.ptr(rois), R, stride, int(batch_base), _lib.ptr(num_rois),
             float(spatial_scale), int(pooled_height), int(pooled_width), int(pool_channel), _lib.ptr(top),
@@ -75,6 +77,8 @@ def roi_pool_pair(data_a, scale_a, data_b, scale_b, rois, pooled_height, pooled_
     top, arg_a, arg_b = out
     if arg_a.dtype != arg_b.dtype or arg_a.dtype not in (torch.int16, torch.int32):
         raise ValueError("argmax tensors must both be int32 (flat index) or int16 (pixel index)")
+    if R == 0:  # as roi_pool
+        return top, arg_a, arg_b
     fn = _lib.load().pcnn_roi_pool_fwd_pair_px if arg_a.dtype == torch.int16 else _lib.load().pcnn_roi_pool_fwd_pair
     rc = fn(_lib.ptr(da), Ha, Wa, float(scale_a), _lib.ptr(db), Hb, Wb, float(scale_b), B, C, _lib.ptr(rois), R, stride,
             int(batch_base), _lib.ptr(num_rois), int(pooled_height), int(pooled_width), _lib.ptr(top), _lib.ptr(arg_a),
@@ -95,7 +99,12 @@ def roi_pool_grad(bottom_data, bottom_rois, argmax, grad, pooled_height, pooled_
     lib = _lib.load()
     ws = _lib.workspace(lib.pcnn_roi_pool_bwd_workspace_size(B, R), bottom_data.device, "roi_bwd")
     dd = out if out is not None else torch.empty(bottom_data.shape, dtype=torch.float32, device=bottom_data.device)
-    if argmax.dtype == torch.int16:  # pixel-index argmax of roi_pool_pair(pixel_argmax=True)
+    px = argmax.dtype == torch.int16  # pixel-index argmax of roi_pool_pair(pixel_argmax=True)
+    if R == 0:
+        # zero-row tensors have no pointer for the library's argument check; with R_cap = 0 the
+        # library reads none of the three and writes the all-zero gradient, so the workspace stands in
+        rois = argmax = grad = ws
+    if px:
         if layout != 0 or pool_channel:
             raise ValueError("a pixel-index argmax needs NHWC data and pool_channel 0")
         rc = lib.pcnn_roi_pool_bwd_px(_lib.ptr(grad.contiguous()), _lib.ptr(argmax.contiguous()), B, H, W, C,
