@@ -784,6 +784,46 @@ int pcnn_vertex_loss_compact(const int32_t* label, const float* vertex3, const f
                              int H, int W, int C, float w_inside, float sigma, float grad_scale, float* d_pred,
                              int d_ch, float* loss, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Backward of the class-compact vertex_pred layer: pcnn_vertex_pred_compact,
+ * the 1x1 conv K -> 3C plus bias of lib/networks/vgg16_convs.py:152-163
+ * (conv2d then bias_add, network.py:168-185) evaluated at each pixel's own
+ * class.  Inputs in the forward's layouts: feat (B,H,W,K) f32 NHWC, weights
+ * (K,3C) f32, label (B,H,W) int32, d_vertex3 (B,H,W,3) f32; the forward's
+ * domain: K % 4 == 0, K * 3C * 4 B <= 64 KiB, B*H*W*K < 2^31; feat, d_vertex3
+ * and d_feat 16-byte aligned.  With g = d_vertex3[p], l = label[p], a pixel is
+ * live if 0 <= l < C:
+ *    d_feat (B,H,W,K)   t = g0 * w[k][3l]; t = t + g1 * w[k][3l+1];
+ *                       t = t + g2 * w[k][3l+2], every op rounded separately;
+ *                       zeros at a pixel that is not live
+ *    d_weights (K,3C)   d_weights[k][3l+j] = sum of feat[p][k] * g_j over the
+ *                       live pixels of class l
+ *    d_bias (3C)        d_bias[3l+j] = sum of g_j over the same pixels
+ * With `label` the ground-truth label map these are the reference's gradients
+ * under the loss's own mask (smooth_l1_loss_vertex, train.py:565-574, whose
+ * vertex_weights are zero off the ground-truth class's three channels).
+ * Sums: float32 products and float32 sums in a fixed order without
+ * floating-point atomics: each range of 2048 pixels is summed into a partial
+ * in the workspace (pcnn_vertex_pred_compact_bwd_partials of them) and the
+ * partials are added in range order, so two runs give the same bits.  A pixel
+ * whose three gradients are all zero is skipped without reading feat, so NaN
+ * or infinite inputs are outside the numerical contract (no out-of-bounds
+ * access follows) and the sign of a zero result is not pinned.  Every element
+ * of every requested output is written, zeros for a class with no pixel.
+ * Each output may be NULL, at least one is required; feat may be NULL when
+ * d_weights is, weights when d_feat is, the workspace when only d_feat is
+ * asked for.  The op runs on `stream`, allocates nothing, reads nothing back
+ * and can be captured in a HIP graph.  PCNN_EINVAL: a NULL required pointer,
+ * a non-positive or out-of-domain dimension, misalignment; PCNN_ECAPACITY: a
+ * short workspace.  The two queries return 0 for dimensions the op rejects.
+ * ------------------------------------------------------------------------- */
+size_t pcnn_vertex_pred_compact_bwd_workspace_size(int B, int H, int W, int K, int C);
+int pcnn_vertex_pred_compact_bwd_partials(int B, int H, int W, int K, int C);
+int pcnn_vertex_pred_compact_bwd(const float* feat, const float* weights, const int32_t* label,
+                                 const float* d_vertex3, int B, int H, int W, int K, int C, float* d_feat,
+                                 float* d_weights, float* d_bias, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

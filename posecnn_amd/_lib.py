@@ -168,6 +168,10 @@ _SIGS = {
     "pcnn_vertex_loss_compact_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "pcnn_vertex_loss_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                          c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcnn_vertex_pred_compact_bwd_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "pcnn_vertex_pred_compact_bwd_partials": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "pcnn_vertex_pred_compact_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -5,7 +5,8 @@
 // 4: the mesh rasteriser (pcnn_render_workspace_size, pcnn_render_meshes)
 // 5: the segmentation and vertex losses (pcnn_seg_loss, pcnn_cross_entropy, pcnn_vertex_loss,
 //    pcnn_vertex_loss_compact and their workspace queries)
-extern "C" int pcnn_abi_version(void) { return 5; }
+// 6: the backward of the class-compact vertex_pred layer (pcnn_vertex_pred_compact_bwd and its two queries)
+extern "C" int pcnn_abi_version(void) { return 6; }
 
 extern "C" const char* pcnn_strerror(int code) {
   switch (code) {
