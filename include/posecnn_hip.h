@@ -444,6 +444,41 @@ int pcnn_pose_head_bwd(const float* d_pred, const float* d_pred_scale, const flo
                        const float* poses_weight, const float* pred, int R_cap, const int32_t* num_rois_dev, int D,
                        float* d_y8, void* stream);
 
+/* The fc7 -> fc8 -> pose head chain of the pose step with fc8 (4C = D <= 128
+ * columns) fused into the split-K reduces around it (fc8_fused.hip).  Bit for
+ * bit pcnn_gemm_drop_gen / pcnn_gemm_drop (fc7 forward) -> pcnn_gemm (fc8
+ * forward) -> pcnn_pose_head_fwd, and pcnn_gemm_drop (fc8 dX), at precision 2.
+ *
+ * pcnn_gemm_partial: pcnn_gemm's GEMM kernel without the reduce pass that
+ *  would follow it: split-K partial slabs [S][M][N] stay in `workspace` (when
+ *  the plan runs whole tiles, C holds bias / act applied).
+ * pcnn_fc8_fwd_fused: after pcnn_gemm_partial of the fc7 forward (M, N7, K7,
+ *  same M_dev, fc7_workspace): forms y7 (M, ld7) = dropout(act7(sum of slabs +
+ *  b7)) -- keep bits given in `drop`, or drawn into it (drop_gen: seed,
+ *  *step_dev, stream_id as pcnn_gemm_drop_gen), or none (keep_prob 1, drop
+ *  NULL) -- while staging it as the A operand of y7 @ W8 (N7, ldb >= D), and
+ *  leaves fc8's split-K partials in fc8_workspace (at least
+ *  pcnn_gemm_workspace_size(M, D, N7, M_dev != NULL, 2) bytes, distinct from
+ *  fc7_workspace).  N7 % 4 == 0, 16-byte aligned rows.
+ * pcnn_fc8_reduce_head_fwd: y8 (R_cap, D) = slabs of fc8_workspace in slice
+ *  order + b8, then pcnn_pose_head_fwd's row pass on it.  K = N7.
+ * pcnn_fc8_dx_skinny: dy7 (M, ldc >= N7) = (mask > 0 ? dy8 (M, lda >= D) @
+ *  W8 (N7, ldb >= D)^T : 0) / keep_prob; D % 4 == 0.  Takes the completion
+ *  event (pcnn_set_completion_event). */
+int pcnn_gemm_partial(int M, int N, int K, const float* A, const float* A2, int lda, int a_trans, const float* B,
+                      int ldb, int b_trans, float* Cm, int ldc, const float* bias, int act, const int32_t* M_dev,
+                      const int32_t* K_dev, int precision, void* workspace, size_t workspace_bytes, void* stream);
+int pcnn_fc8_fwd_fused(int M, int N7, int K7, const void* fc7_workspace, size_t fc7_workspace_bytes, const float* b7,
+                       int act7, float* y7, int ld7, uint8_t* drop, int ldd, float keep_prob, int drop_gen,
+                       uint64_t seed, const int64_t* step_dev, int stream_id, const float* W8, int ldb, int D,
+                       const int32_t* M_dev, void* fc8_workspace, size_t fc8_workspace_bytes, void* stream);
+int pcnn_fc8_reduce_head_fwd(const void* fc8_workspace, size_t fc8_workspace_bytes, const float* b8, int R_cap, int K,
+                             int D, const int32_t* num_rois_dev, const float* poses_weight, float* y8,
+                             float* tanh_out, float* pred, void* stream);
+int pcnn_fc8_dx_skinny(const float* dy8, int lda, const float* W8, int ldb, const float* mask, int ldm,
+                       float keep_prob, float* dy7, int ldc, int M, int D, int N7, const int32_t* M_dev,
+                       void* stream);
+
 /* ---------------------------------------------------------------------------
  * Class-aware greedy box NMS + pose combination (inference consumer of the
  * Hough rows).

@@ -110,6 +110,16 @@ _SIGS = {
     "pcnn_hard_label_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "pcnn_vertex_pred_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                          c_void_p, c_void_p]),
+    "pcnn_gemm_partial": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                  c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                  c_void_p]),
+    "pcnn_fc8_fwd_fused": (c_int, [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                   c_int, c_float, c_int, ctypes.c_uint64, c_void_p, c_int, c_void_p, c_int, c_int,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcnn_fc8_reduce_head_fwd": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pcnn_fc8_dx_skinny": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_int,
+                                   c_int, c_int, c_void_p, c_void_p]),
     "pcnn_pose_head_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "pcnn_pose_head_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                    c_void_p]),

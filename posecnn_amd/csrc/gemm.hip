@@ -117,7 +117,7 @@ static int gemm_impl(int M, int N, int K, const float* A, const float* A2, int l
                      int ldb, int b_trans, float* Cm, int ldc, const float* bias, int act, const float* mask, int ldm,
                      const uint8_t* drop, int ldd, float keep_prob, const int32_t* M_dev, const int32_t* K_dev,
                      int precision, void* workspace, size_t workspace_bytes, void* stream, int drop_gen,
-                     uint64_t seed, const int64_t* step_dev, int stream_id) {
+                     uint64_t seed, const int64_t* step_dev, int stream_id, bool skip_reduce = false) {
   PCNN_REQUIRE(M >= 0 && N > 0 && K >= 0 && A && B && Cm);
   PCNN_REQUIRE(!drop_gen || (drop && N % 4 == 0 && ldd % 4 == 0 && ((uintptr_t)drop & 3) == 0 && stream_id >= 0 &&
                              (long)M * (N / 4) < (1l << 31)));
@@ -148,7 +148,7 @@ static int gemm_impl(int M, int N, int K, const float* A, const float* A2, int l
   hipStream_t st = (hipStream_t)stream;
   // the op's completion event goes to whichever launch is last: held back
   // from the GEMM kernel when a reduce follows
-  const bool reduce_after = reduce_follows(plan, precision, drop, keep_prob);
+  const bool reduce_after = !skip_reduce && reduce_follows(plan, precision, drop, keep_prob);
   if (precision == 0) {
     launch_gemm_f32(g, a_trans, b_trans, st);
     if (reduce_after) launch_gemm_reduce(g, st);
@@ -189,4 +189,12 @@ extern "C" int pcnn_gemm_drop_gen(int M, int N, int K, const float* A, const flo
   return gemm_impl(M, N, K, A, A2, lda, a_trans, B, ldb, b_trans, Cm, ldc, bias, act, nullptr, 0, drop_out, ldd,
                    keep_prob, M_dev, K_dev, precision, workspace, workspace_bytes, stream, 1, seed, step_dev,
                    stream_id);
+}
+
+extern "C" int pcnn_gemm_partial(int M, int N, int K, const float* A, const float* A2, int lda, int a_trans,
+                                 const float* B, int ldb, int b_trans, float* Cm, int ldc, const float* bias, int act,
+                                 const int32_t* M_dev, const int32_t* K_dev, int precision, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  return gemm_impl(M, N, K, A, A2, lda, a_trans, B, ldb, b_trans, Cm, ldc, bias, act, nullptr, 0, nullptr, 0, 1.f,
+                   M_dev, K_dev, precision, workspace, workspace_bytes, stream, 0, 0, nullptr, 0, true);
 }

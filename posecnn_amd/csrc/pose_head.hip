@@ -39,26 +39,13 @@ __global__ void __launch_bounds__(256) k_head_fwd(const float* __restrict__ y8, 
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = pcnn::lane_id();
   if (row >= R) return;
-  float mv[4];
-  float ss = 0.f;
+  float y[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const int c = lane + 64 * k;
-    mv[k] = 0.f;
-    if (c < D) {
-      const float t = tanhf(y8[(size_t)row * D + c]);
-      t_out[(size_t)row * D + c] = t;
-      mv[k] = t * pw[(size_t)row * D + c];
-      ss += mv[k] * mv[k];
-    }
+    y[k] = c < D ? y8[(size_t)row * D + c] : 0.f;
   }
-  ss = pcnn::wave_sum(ss);
-  const float inv = 1.f / sqrtf(fmaxf(ss, 1e-12f));  // tf.nn.l2_normalize
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int c = lane + 64 * k;
-    if (c < D) pred[(size_t)row * D + c] = mv[k] * inv;
-  }
+  pcnn_head::head_fwd_row(y, pw, row, D, lane, t_out, pred);
 }
 
 __global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ dpred, const float* __restrict__ t_in,

@@ -45,7 +45,7 @@ class PoseStep:
                  global_batch=None, batch_base=0, weights=None, dist=None, backward=True, precision=2,
                  overlap_weight_grads=True, pixel_argmax=True, keep_prob=None, drop_seed=0x5EED, side_prep=True,
                  drop_in_reduce=True, pipeline=False, prefetch_at="loss", fuse_loss_tail=True,
-                 defer_side_join=False, signal_forks=True, pool_at_tail=False):
+                 defer_side_join=False, signal_forks=True, pool_at_tail=False, fuse_fc8=True):
         self.B, self.H, self.W, self.C = B, H, W, num_classes
         self.dev = device
         self.is_train, self.skip, self.vthr, self.vper, self.margin = is_train, skip_pixels, vote_threshold, \
@@ -62,6 +62,11 @@ class PoseStep:
         self.Ch = channels
         D = 4 * num_classes
         self.D = D
+        # fc8 (4C <= 128 columns, precision 2) fused into the split-K reduces
+        # around it and its dX as the skinny kernel (fc8_fused.hip): the same
+        # bits in fewer, shorter launches on the step's latency chain.  False:
+        # the generic GEMM launches (A/B).  The image-sharded step keeps those.
+        self.fuse_fc8 = bool(fuse_fc8) and dist is None and ph.fc8_fused_ok(units, D, precision) and D % 4 == 0
         self.weights = weights or ph.PoseHeadWeights(num_classes, device, in_dim=49 * channels, units=units)
         f32 = dict(dtype=torch.float32, device=device)
         i32 = dict(dtype=torch.int32, device=device)
@@ -449,10 +454,24 @@ class PoseStep:
         if gs is not None:
             gs.send_input("w7", self.y6)
         with self._t("gemm_fc7_fc8_fwd"):
-            self._g("fc7_fwd", self.y6, w.w7, self.y7, bias=w.b7, act=1, M_dev=nr, drop=self.drop7, **dk, **g7)
-            if gs is not None:
-                gs.send_input("w8", self.y7)
-            self._g("fc8_fwd", self.y7, w.w8, self.y8, bias=w.b8, act=0, M_dev=nr)
+            if self.fuse_fc8:
+                # the fc7 GEMM alone; its reduce runs inside the fc8 forward's
+                # staging, fc8's reduce inside the pose head's row pass
+                ws7 = self._timed_gemm("fc7_fwd", lambda: ph.gemm_partial(self.y6, w.w7, self.y7, bias=w.b7, act=1,
+                                                                          M_dev=nr, precision=self.prec))
+
+                def fc8_head():
+                    ph.fc8_fwd_fused(ws7, w.units, w.b7, self.y7, w.w8, act=1, drop=self.drop7,
+                                     drop_gen=g7.get("drop_gen"), M_dev=nr, **dk)
+                    if gs is not None:
+                        gs.send_input("w8", self.y7)
+                    ph.fc8_reduce_head_fwd(w.b8, w.units, h["weight"], self.y8, self.t8, self.pred, num_rois=nr)
+                self._timed_gemm("fc8_fwd", fc8_head)
+            else:
+                self._g("fc7_fwd", self.y6, w.w7, self.y7, bias=w.b7, act=1, M_dev=nr, drop=self.drop7, **dk, **g7)
+                if gs is not None:
+                    gs.send_input("w8", self.y7)
+                self._g("fc8_fwd", self.y7, w.w8, self.y8, bias=w.b8, act=0, M_dev=nr)
         if self.prefetch_at == "loss":  # the next minibatch's vote + pool beside the loss and the backward
             self._prefetch()
         if gen:  # the step counter moves on once both masks are drawn
@@ -464,7 +483,8 @@ class PoseStep:
             self._wait("rows")
             self.norm_rows.clamp_(min=1)
         with self._t("head_add_loss_fwd"):
-            ph.head_fwd(self.y8, h["weight"], self.t8, self.pred, num_rois=nr)
+            if not self.fuse_fc8:  # (fused: done with fc8's reduce)
+                ph.head_fwd(self.y8, h["weight"], self.t8, self.pred, num_rois=nr)
             if not st["prepped"]:  # forward() called without step()
                 self.add_prep(points, symmetry)
             if st["prepped"] == "side":
@@ -553,7 +573,11 @@ class PoseStep:
         dk = dict(keep_prob=self.keep) if self.keep < 1.0 else {}  # relu + dropout backward: kept grads / keep_prob
         ev = self._arm_fork("fc8_dx") if side is not None else None
         with self._t("gemm_fc8_fc7_dx"):
-            self._g("fc8_dx", self.dy8, w.w8, self.dy7, b_trans=1, mask=self.y7, M_dev=nr, **dk)
+            if self.fuse_fc8:
+                self._timed_gemm("fc8_dx", lambda: ph.fc8_dx(self.dy8, w.w8, self.dy7, mask=self.y7, M_dev=nr,
+                                                             precision=self.prec, **dk))
+            else:
+                self._g("fc8_dx", self.dy8, w.w8, self.dy7, b_trans=1, mask=self.y7, M_dev=nr, **dk)
         ev = self._fork_taken(ev)
         with self._t("gemm_fc8_fc7_dw_bias"):  # fc7 weight / bias gradients
             weight_grads("w7", self.y6, self.dy7, CAP, w.units, w.units, fork_ev=ev)
@@ -603,14 +627,19 @@ class PoseStep:
     def _g(self, name, A, B, C, **kw):
         """One FC GEMM at the step's precision, bracketed by HIP events on the
         stream it is launched on when gemm_timer is set."""
+        self._timed_gemm(name, lambda: ph.gemm(A, B, C, precision=self.prec, **kw))
+        return C
+
+    def _timed_gemm(self, name, launch):
+        """launch() bracketed by HIP events under the GEMM timer key `name`."""
         if self.gemm_timer is None:
-            return ph.gemm(A, B, C, precision=self.prec, **kw)
+            return launch()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        ph.gemm(A, B, C, precision=self.prec, **kw)
+        out = launch()
         e1.record()
         self.gemm_timer.setdefault(name, []).append((e0, e1))
-        return C
+        return out
 
     def step(self, inputs, next_inputs=None):
         """One training step over the minibatch `inputs`.

@@ -132,6 +132,114 @@ def head_fwd(y8, poses_weight, tanh_out, pred, num_rois=None, stream=None):
     _lib.check(rc, "pose_head_fwd")
 
 
+FC8_FUSED_MAX_D = 128  # columns the fused fc8 kernels take (one wave per 32-column block)
+
+
+def fc8_fused_ok(units, D, precision=2):
+    """Whether the fc8 kernels fused into the split-K reduces (fc8_fused.hip)
+    take this shape; otherwise the chain runs as gemm / gemm / head_fwd."""
+    return precision == 2 and 0 < D <= FC8_FUSED_MAX_D and units % 4 == 0
+
+
+def gemm_partial(A, B, C, bias=None, act=0, M_dev=None, precision=2, stream=None):
+    """gemm()'s GEMM kernel without the reduce pass after it (pcnn_gemm_partial):
+    the split-K partial slabs stay in the stream's GEMM workspace, which is
+    returned for fc8_fwd_fused."""
+    _lib.require_gpu(A, B, C)
+    for t in (A, B, C, bias):
+        if t is not None and (t.dtype != torch.float32 or t.stride(-1) != 1):
+            raise ValueError("gemm operands must be fp32 with unit inner stride")
+    M, K = A.shape
+    N = B.shape[1]
+    lib = _lib.load()
+    ws = _lib.workspace(lib.pcnn_gemm_workspace_size(M, N, K, int(M_dev is not None), precision), C.device, "gemm",
+                        stream)
+    rc = lib.pcnn_gemm_partial(M, N, K, _lib.ptr(A), None, A.stride(0), 0, _lib.ptr(B), B.stride(0), 0, _lib.ptr(C),
+                               C.stride(0), _lib.ptr(bias), int(act), _lib.ptr(M_dev), None, int(precision),
+                               _lib.ptr(ws), ws.numel(), _lib.stream_ptr(stream))
+    _lib.check(rc, "gemm_partial")
+    return ws
+
+
+def _fc8_workspace(M, D, K, M_dev, device, stream):
+    nbytes = max(_lib.load().pcnn_gemm_workspace_size(M, D, K, int(M_dev is not None), 2), M * D * 4)
+    return _lib.workspace(nbytes, device, "fc8", stream)
+
+
+def fc8_fwd_fused(fc7_ws, K7, b7, y7, W8, act=1, drop=None, keep_prob=1.0, drop_gen=None, M_dev=None, stream=None):
+    """After gemm_partial (the fc7 forward, workspace fc7_ws, contraction K7):
+    y7 = dropout(act(slab sum + b7)) formed while it is staged as the A operand
+    of y7 @ W8; fc8's split-K partials stay in the stream's fc8 workspace for
+    fc8_reduce_head_fwd (pcnn_fc8_fwd_fused).  drop / keep_prob / drop_gen as gemm()."""
+    _lib.require_gpu(fc7_ws, y7, W8)
+    M, N7 = y7.shape
+    D = W8.shape[1]
+    if drop is not None and (drop.dtype != torch.uint8 or drop.stride(-1) != 1 or not drop.is_cuda):
+        raise ValueError("fc8_fwd_fused: drop must be a uint8 device tensor with unit inner stride")
+    seed, step_dev, sid = drop_gen if drop_gen is not None else (0, None, 0)
+    if step_dev is not None and (step_dev.dtype != torch.int64 or not step_dev.is_cuda):
+        raise ValueError("fc8_fwd_fused: drop_gen's step counter must be an int64 device tensor")
+    ws8 = _fc8_workspace(M, D, N7, M_dev, y7.device, stream)
+    rc = _lib.load().pcnn_fc8_fwd_fused(M, N7, int(K7), _lib.ptr(fc7_ws), fc7_ws.numel(), _lib.ptr(b7), int(act),
+                                        _lib.ptr(y7), y7.stride(0), _lib.ptr(drop),
+                                        drop.stride(0) if drop is not None else 0, float(keep_prob),
+                                        int(drop_gen is not None), int(seed) & ((1 << 64) - 1), _lib.ptr(step_dev),
+                                        int(sid), _lib.ptr(W8), W8.stride(0), D, _lib.ptr(M_dev), _lib.ptr(ws8),
+                                        ws8.numel(), _lib.stream_ptr(stream))
+    _lib.check(rc, "fc8_fwd_fused")
+
+
+def fc8_reduce_head_fwd(b8, K, poses_weight, y8, tanh_out, pred, num_rois=None, stream=None):
+    """y8 = fc8's split-K partials (left by fc8_fwd_fused on this stream) in
+    slice order + b8, and head_fwd on it, in one row pass (pcnn_fc8_reduce_head_fwd)."""
+    R, D = y8.shape
+    if not (y8.is_contiguous() and tanh_out.is_contiguous() and pred.is_contiguous() and
+            poses_weight.is_contiguous()):
+        raise ValueError("fc8_reduce_head_fwd: contiguous (R, D) rows")
+    ws8 = _fc8_workspace(R, D, K, num_rois, y8.device, stream)
+    rc = _lib.load().pcnn_fc8_reduce_head_fwd(_lib.ptr(ws8), ws8.numel(), _lib.ptr(b8), R, int(K), D,
+                                              _lib.ptr(num_rois), _lib.ptr(poses_weight), _lib.ptr(y8),
+                                              _lib.ptr(tanh_out), _lib.ptr(pred), _lib.stream_ptr(stream))
+    _lib.check(rc, "fc8_reduce_head_fwd")
+
+
+def fc8_dx(dy8, W8, dy7, mask=None, keep_prob=1.0, M_dev=None, precision=2, stream=None):
+    """dy7 = (mask > 0 ? dy8 @ W8^T : 0) / keep_prob: the skinny kernel
+    (pcnn_fc8_dx_skinny) where it applies, else gemm(b_trans=1); the same bits."""
+    D = W8.shape[1]
+    if not (fc8_fused_ok(W8.shape[0], D, precision) and D % 4 == 0):
+        return gemm(dy8, W8, dy7, b_trans=1, mask=mask, M_dev=M_dev, precision=precision, keep_prob=keep_prob,
+                    stream=stream)
+    _lib.require_gpu(dy8, W8, dy7, mask)
+    for t in (dy8, W8, dy7, mask):
+        if t is not None and (t.dtype != torch.float32 or t.stride(-1) != 1):
+            raise ValueError("gemm operands must be fp32 with unit inner stride")
+    rc = _lib.load().pcnn_fc8_dx_skinny(_lib.ptr(dy8), dy8.stride(0), _lib.ptr(W8), W8.stride(0), _lib.ptr(mask),
+                                        mask.stride(0) if mask is not None else 0, float(keep_prob), _lib.ptr(dy7),
+                                        dy7.stride(0), dy8.shape[0], D, W8.shape[0], _lib.ptr(M_dev),
+                                        _lib.stream_ptr(stream))
+    _lib.check(rc, "fc8_dx_skinny")
+    return dy7
+
+
+def fc7_fc8_head_fwd(y6, w7, b7, y7, w8, b8, y8, poses_weight, tanh_out, pred, drop=None, keep_prob=1.0,
+                     drop_gen=None, M_dev=None, precision=2, fuse=True, stream=None):
+    """fc7 (relu, dropout) -> fc8 -> pose head forward.  4C <= 128 columns at
+    precision 2: the fc7 GEMM, then two launches (fc8_fwd_fused,
+    fc8_reduce_head_fwd); otherwise gemm, gemm, head_fwd -- the same bits."""
+    dk = dict(keep_prob=keep_prob) if keep_prob < 1.0 else {}
+    if fuse and fc8_fused_ok(w7.shape[1], w8.shape[1], precision):
+        ws7 = gemm_partial(y6, w7, y7, bias=b7, act=1, M_dev=M_dev, precision=precision, stream=stream)
+        fc8_fwd_fused(ws7, w7.shape[0], b7, y7, w8, act=1, drop=drop, drop_gen=drop_gen, M_dev=M_dev, stream=stream,
+                      **dk)
+        fc8_reduce_head_fwd(b8, w8.shape[0], poses_weight, y8, tanh_out, pred, num_rois=M_dev, stream=stream)
+        return
+    gemm(y6, w7, y7, bias=b7, act=1, M_dev=M_dev, drop=drop, drop_gen=drop_gen, precision=precision, stream=stream,
+         **dk)
+    gemm(y7, w8, y8, bias=b8, act=0, M_dev=M_dev, precision=precision, stream=stream)
+    head_fwd(y8, poses_weight, tanh_out, pred, num_rois=M_dev, stream=stream)
+
+
 def head_bwd(d_pred, tanh_out, poses_weight, pred, d_y8, num_rois=None, d_pred_scale=None, stream=None):
     """d_y8 from d_pred; with d_pred_scale (device scalar) d_pred is taken as
     d_pred_scale[0] * d_pred -- the ADD-loss gradient op folded into this pass."""
