@@ -859,6 +859,73 @@ int pcnn_vertex_pred_compact_bwd(const float* feat, const float* weights, const 
                                  float* d_weights, float* d_bias, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The upscore layers: the reference's fixed bilinear transposed conv
+ * (`upscore`, `upscore_vertex`: 16x16 at stride 8, lib/networks/
+ * vgg16_convs.py:138,162; `upscore_conv5(_vertex)`: 4x4 at stride 2,
+ * :122,130,154; filter network.py:141-157, layer :207-222), generic and
+ * folded behind the 1x1 conv it feeds.
+ *
+ * x (B,h,w,Ch) f32 NHWC, stride s in {2,4,8,16}, kernel 2s x 2s, SAME padding:
+ * y (B, H = s h, W = s w, Ch).  Output row yo has the taps
+ *    i1 = (yo + s/2) div s,  k = yo + s/2 - s i1,  i0 = i1 - 1,
+ *    weight (2k+1)/(2s) at i1, (2s-1-2k)/(2s) at i0;
+ * a tap with i0 < 0 or i1 >= h is absent (zero padding, not clamping);
+ * columns alike; a 2-D weight is the product of its row and column weights
+ * (exact).  The generic forward's pinned order, every op rounded separately:
+ *    acc = ((t00 + t01) + t10) + t11,  t = x[tap] * weight,
+ * taps in the order (i0,j0), (i0,j1), (i1,j0), (i1,j1), absent taps skipped,
+ * the first present term starts the sum; then acc + bias[ch] if bias is not
+ * NULL; then acc > 0 ? acc : 0 if relu.
+ *
+ * pcnn_upscore_fwd         the layer above.
+ * pcnn_upscore_bwd         d_x[i,j,ch] = sum of weight * m * d_y over the at
+ *                          most (2s)^2 outputs that tap (i,j), m = (y > 0)
+ *                          with y the forward's output, m = 1 if y is NULL;
+ *                          d_bias[ch] = sum of m * d_y (NULL: not computed;
+ *                          the workspace may then be NULL).  The order of the
+ *                          sums is the device's own and fixed: rows then
+ *                          columns for d_x, per-workgroup partials added in
+ *                          range order for d_bias.
+ * pcnn_upscore_compact_fwd z (B,h,w,3C), bias (3C), label (B,H,W) int32 ->
+ *                          vertex3 (B,H,W,3): vertex3[p][j] is the generic
+ *                          forward of z with bias and without ReLU at channel
+ *                          3l+j for l = label[p] in [0,C), bit for bit; zeros
+ *                          for any other label.  With z = x W this is
+ *                          vertex_pred(upscore_vertex(x)) at the pixel's own
+ *                          class with the two linear layers commuted: equal
+ *                          in exact arithmetic, different by float32 rounding.
+ * pcnn_upscore_compact_bwd d_z[i,j,3c+k] = sum over the pixels p of the
+ *                          window of (i,j) with label[p] = c of weight *
+ *                          d_vertex3[p][k]; every one of the 3C channels is
+ *                          written, zeros for a class without a pixel there.
+ *                          d_bias[3c+k] = sum of d_vertex3[p][k] over the
+ *                          pixels of class c.  Either output may be NULL, not
+ *                          both; the workspace may be NULL without d_bias.
+ *
+ * Domain: B, h, w, Ch (C) > 0; B*H*W*max(Ch,3) < 2^31 (compact: Ch = 3, and
+ * B*h*w*3C < 2^31, C <= 1024).  The generic pair's full-resolution maps (y,
+ * d_y and the mask) are 16-byte aligned.  No floating-point atomics:
+ * two runs give the same bits.  NaN or infinite inputs are outside the
+ * numerical contract (no out-of-bounds access follows); the sign of a zero
+ * sum of the backward ops is not pinned.  Every element of every requested
+ * output is written.  The ops run on `stream`, allocate nothing, read nothing
+ * back and can be captured in a HIP graph.  PCNN_EINVAL: a NULL required
+ * pointer, a stride not in {2,4,8,16}, a non-positive or out-of-domain
+ * dimension, misalignment; PCNN_ECAPACITY: a short workspace.  The workspace
+ * queries return 0 for dimensions the ops reject.
+ * ------------------------------------------------------------------------- */
+int pcnn_upscore_fwd(const float* x, int B, int h, int w, int Ch, int stride, const float* bias, int relu, float* y,
+                     void* stream);
+size_t pcnn_upscore_bwd_workspace_size(int B, int h, int w, int Ch, int stride);
+int pcnn_upscore_bwd(const float* d_y, const float* y, int B, int h, int w, int Ch, int stride, float* d_x,
+                     float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
+int pcnn_upscore_compact_fwd(const float* z, const float* bias, const int32_t* label, int B, int h, int w, int C,
+                             int stride, float* vertex3, void* stream);
+size_t pcnn_upscore_compact_bwd_workspace_size(int B, int h, int w, int C, int stride);
+int pcnn_upscore_compact_bwd(const int32_t* label, const float* d_vertex3, int B, int h, int w, int C, int stride,
+                             float* d_z, float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

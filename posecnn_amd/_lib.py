@@ -182,6 +182,15 @@ _SIGS = {
     "pcnn_vertex_pred_compact_bwd_partials": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "pcnn_vertex_pred_compact_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcnn_upscore_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "pcnn_upscore_bwd_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "pcnn_upscore_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
+    "pcnn_upscore_compact_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                         c_void_p]),
+    "pcnn_upscore_compact_bwd_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "pcnn_upscore_compact_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
 }
 
 

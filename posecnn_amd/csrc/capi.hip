@@ -6,7 +6,9 @@
 // 5: the segmentation and vertex losses (pcnn_seg_loss, pcnn_cross_entropy, pcnn_vertex_loss,
 //    pcnn_vertex_loss_compact and their workspace queries)
 // 6: the backward of the class-compact vertex_pred layer (pcnn_vertex_pred_compact_bwd and its two queries)
-extern "C" int pcnn_abi_version(void) { return 6; }
+// 7: the upscore layers (pcnn_upscore_fwd, pcnn_upscore_bwd, pcnn_upscore_compact_fwd, pcnn_upscore_compact_bwd
+//    and the two workspace queries)
+extern "C" int pcnn_abi_version(void) { return 7; }
 
 extern "C" const char* pcnn_strerror(int code) {
   switch (code) {

@@ -24,6 +24,16 @@ and the class-compact vertex_pred layer (posecnn_amd.vertex_pred) as a
 trainable module:
 
     VertexPredCompact(num_units, num_classes)(feat_NHWC, label) -> (B,H,W,3)
+
+The upscore layers in front of both heads (posecnn_amd.upscore), and the two
+heads with the upscore folded behind their 1x1 conv (x_low is the feature map
+at 1/stride resolution, the (B,H,W,num_units) map between the layers is never
+formed; equal to the reference's order in exact arithmetic, different from it
+by float32 rounding):
+
+    Upscore(stride, relu=False)(x_NHWC) -> (B, stride*h, stride*w, Ch)
+    VertexHeadCompact(num_units, num_classes, stride=8)(x_low, label) -> (B,H,W,3)
+    ScoreHead(num_units, num_classes, stride=8)(x_low) -> score (B,H,W,C)
 """
 import torch
 from torch import nn
@@ -33,6 +43,7 @@ from .roi_pooling_layer import roi_pooling_op as rp
 from .average_distance_loss import average_distance_loss_op as adl
 from . import losses
 from . import vertex_pred as vp
+from . import upscore as up
 
 
 class HoughVoting(nn.Module):
@@ -203,6 +214,113 @@ class VertexPredCompact(nn.Module):
         if feat.dim() != 4 or feat.shape[3] != self.num_units:
             raise ValueError(f"feat must be (B,H,W,{self.num_units}), got {tuple(feat.shape)}")
         return _VertexPredCompactFn.apply(feat, self.weight, self.bias, label)
+
+
+class _UpscoreFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bias, stride, relu):
+        y = up.upscore(x, stride, bias=bias, relu=relu)
+        ctx.save_for_backward(*([y] if relu else []))
+        ctx.params = (stride, relu, x.dtype, None if bias is None else bias.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        stride, relu, x_dtype, b_dtype = ctx.params
+        y = ctx.saved_tensors[0] if relu else None
+        want_bias = b_dtype is not None and ctx.needs_input_grad[1]
+        if not ctx.needs_input_grad[0] and not want_bias:
+            return None, None, None, None
+        d = up.upscore_bwd(grad, stride, y=y, want_bias=want_bias)
+        d_x, d_b = d if want_bias else (d, None)
+        return (d_x.to(x_dtype) if ctx.needs_input_grad[0] else None, d_b.to(b_dtype) if want_bias else None, None,
+                None)
+
+
+class Upscore(nn.Module):
+    """The reference's fixed bilinear deconv (network.py:207-222 with
+    trainable=False: a 2*stride square kernel at `stride`, SAME padding):
+    x (B,h,w,Ch) NHWC -> (B, stride*h, stride*w, Ch).  stride 8 is `upscore` /
+    `upscore_vertex`, stride 2 `upscore_conv5(_vertex)`."""
+
+    def __init__(self, stride, relu=False):
+        super().__init__()
+        if stride not in up.STRIDES:
+            raise ValueError(f"stride must be one of {up.STRIDES}, got {stride}")
+        self.stride = int(stride)
+        self.relu = bool(relu)
+
+    def forward(self, x):
+        return _UpscoreFn.apply(x, None, self.stride, self.relu)
+
+
+class _UpscoreCompactFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, bias, label, stride):
+        ctx.save_for_backward(label)
+        ctx.params = (stride, z.shape[3] // 3, z.dtype, bias.dtype)
+        return up.upscore_compact(z, bias, label, stride)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (label,) = ctx.saved_tensors
+        stride, C, z_dtype, b_dtype = ctx.params
+        want = tuple(n for n, need in zip(up.COMPACT_BWD_OUTPUTS, ctx.needs_input_grad[:2]) if need)
+        if not want:
+            return None, None, None, None
+        d = up.upscore_compact_bwd(label, grad, C, stride, want=want)
+        return (d["z"].to(z_dtype) if "z" in d else None, d["bias"].to(b_dtype) if "bias" in d else None, None, None)
+
+
+class VertexHeadCompact(nn.Module):
+    """`upscore_vertex` and `vertex_pred` (vgg16_convs.py:152-163) as one head
+    evaluated at each pixel's own class: (x_low (B,h,w,num_units) NHWC, label
+    (B, stride*h, stride*w) integer) -> (B,H,W,3).  Both layers are linear and
+    the upscore is depthwise, so the 1x1 conv runs first, at low resolution
+    (z = x_low @ weight, a torch matmul), and the upscore of z plus bias is
+    taken at the three channels of the pixel's class.  Parameters as
+    VertexPredCompact's (state dicts interchange); differentiable in x_low,
+    weight and bias."""
+
+    def __init__(self, num_units, num_classes, stride=8):
+        super().__init__()
+        if stride not in up.STRIDES:
+            raise ValueError(f"stride must be one of {up.STRIDES}, got {stride}")
+        self.num_units = int(num_units)
+        self.num_classes = int(num_classes)
+        self.stride = int(stride)
+        self.weight = nn.Parameter(torch.empty(self.num_units, 3 * self.num_classes))
+        self.bias = nn.Parameter(torch.zeros(3 * self.num_classes))
+        nn.init.trunc_normal_(self.weight, std=0.001, a=-0.002, b=0.002)  # network.py:170, biases 0 (:183)
+
+    def forward(self, x_low, label):
+        if x_low.dim() != 4 or x_low.shape[3] != self.num_units:
+            raise ValueError(f"x_low must be (B,h,w,{self.num_units}), got {tuple(x_low.shape)}")
+        z = torch.matmul(x_low, self.weight)
+        return _UpscoreCompactFn.apply(z, self.bias, label, self.stride)
+
+
+class ScoreHead(nn.Module):
+    """`upscore` and `score` (vgg16_convs.py:138-140: the deconv, then a 1x1
+    conv num_units -> C with ReLU) with the conv first, at low resolution:
+    x_low (B,h,w,num_units) -> relu(upscore(x_low @ weight) + bias), (B,H,W,C),
+    the input of SegmentationLoss.  `weight` is (num_units, C)."""
+
+    def __init__(self, num_units, num_classes, stride=8):
+        super().__init__()
+        if stride not in up.STRIDES:
+            raise ValueError(f"stride must be one of {up.STRIDES}, got {stride}")
+        self.num_units = int(num_units)
+        self.num_classes = int(num_classes)
+        self.stride = int(stride)
+        self.weight = nn.Parameter(torch.empty(self.num_units, self.num_classes))
+        self.bias = nn.Parameter(torch.zeros(self.num_classes))
+        nn.init.trunc_normal_(self.weight, std=0.001, a=-0.002, b=0.002)
+
+    def forward(self, x_low):
+        if x_low.dim() != 4 or x_low.shape[3] != self.num_units:
+            raise ValueError(f"x_low must be (B,h,w,{self.num_units}), got {tuple(x_low.shape)}")
+        return _UpscoreFn.apply(torch.matmul(x_low, self.weight), self.bias, self.stride, True)
 
 
 class AverageDistanceLoss(nn.Module):
