@@ -239,6 +239,52 @@ def require_gpu(*tensors):
             raise ValueError("posecnn_amd ops take device tensors (got a CPU tensor)")
 
 
+def require(t, dtype, shape=None, contiguous=True, name="tensor", optional=False, rows=None):
+    """The wrappers' one argument check ("The tensor contract"):
+    `t` is a device tensor of `dtype` (one dtype or a tuple of them) and, if
+    given, of `shape` (None entries are free).  contiguous=True: packed;
+    False: unit inner stride only (an operand passed with its leading
+    dimension).  rows=(r, c): a 2-D operand whose view holds r rows of c
+    elements at its own row pitch.  Raises ValueError naming the argument
+    (TypeError for a non-tensor); reads attributes only -- no sync, no
+    allocation -- and never copies.  Returns `t`."""
+    if t is None:
+        if optional:
+            return None
+        raise ValueError(f"{name}: a tensor is required (got None)")
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: expected a device tensor (got a CPU tensor)")
+    if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+        raise ValueError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if shape is not None and (t.dim() != len(shape) or
+                              any(s is not None and s != d for s, d in zip(shape, t.shape))):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    if contiguous:
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous tensor, got strides {tuple(t.stride())}")
+    elif t.dim() and t.stride(-1) != 1:
+        raise ValueError(f"{name}: expected unit inner stride, got strides {tuple(t.stride())}")
+    if rows is not None:
+        r, c = rows
+        if t.dim() != 2 or t.shape[1] < c or t.shape[0] < r or (t.shape[0] > 1 and t.stride(0) < c):
+            raise ValueError(f"{name}: expected at least {r} rows of {c} elements, got shape {tuple(t.shape)} "
+                             f"with strides {tuple(t.stride())}")
+    return t
+
+
+def require_counter(t, name, dtype=torch.int32):
+    """An optional device-side counter (num_rois, M_dev, K_dev, rows_dev,
+    loss_norm_rows_dev: int32; step_dev: int64): a contiguous device tensor of
+    the prototype's integer type with at least one element, or None."""
+    if t is not None:
+        require(t, dtype, name=name)
+        if t.numel() < 1:
+            raise ValueError(f"{name}: expected at least one element")
+    return t
+
+
 class _TensorPtr(ctypes.c_void_p):
     __slots__ = ("tensor",)
 

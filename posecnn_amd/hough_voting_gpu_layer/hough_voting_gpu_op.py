@@ -78,6 +78,18 @@ def hough_voting_gpu_capacity(label, vertex, extents, meta_data, gt, is_train, t
             domain=torch.empty((CAPACITY,), dtype=torch.int32, device=dev),
             num_rois=torch.empty((2,), dtype=torch.int32, device=dev),
         )
+    else:  # the caller's buffers are written in place: never copied, checked and refused
+        if not isinstance(out, dict):
+            raise TypeError(f"hough_voting_gpu: out must be a dict of tensors, got {type(out).__name__}")
+        box = _lib.require(out.get("box"), torch.float32, shape=(None, 7), name="hough_voting_gpu: out['box']")
+        cap = box.shape[0]
+        f32, i32 = torch.float32, torch.int32
+        for key, dt, shape in (("box", f32, (cap, 7)), ("pose", f32, (cap, 7)), ("target", f32, (cap, 4 * C)),
+                               ("weight", f32, (cap, 4 * C)), ("domain", i32, (cap,)), ("num_rois", i32, (2,))):
+            _lib.require(out.get(key), dt, shape=shape, name=f"hough_voting_gpu: out[{key!r}]")
+        _lib.require(out.get("label"), i32, shape=(B, H, W), name="hough_voting_gpu: out['label']", optional=True)
+    if debug_counts is not None:
+        _lib.require(debug_counts, torch.int32, shape=(B, C - 1, H, W), name="hough_voting_gpu: debug_counts")
     if prob is not None and out.get("label") is None:
         out["label"] = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     nbytes = lib.pcnn_hough_voting_workspace_size(B, H, W, C, int(skip_pixels), float(threshold_vote))
@@ -144,6 +156,8 @@ def hough_voting_gpu_from_prob(bottom_prob, bottom_vertex, bottom_extents, botto
 def hough_voting_gpu_grad(bottom_label, bottom_vertex, grad, name=None):
     """HoughvotinggpuGrad (hough_voting_gpu_op.cc:440-484): zero gradients."""
     _lib.require_gpu(bottom_label, bottom_vertex)
+    if bottom_label.dim() != 3 or bottom_vertex.dim() != 4:
+        raise ValueError("label must be 3-dimensional and vertex 4-dimensional")
     B, H, W = bottom_label.shape
     C = bottom_vertex.shape[3] // 3
     gl = torch.empty((B, H, W), dtype=torch.float32, device=bottom_label.device)

@@ -20,6 +20,8 @@ def argmax_2d(prob, out=None, stream=None):
     prob = prob.contiguous().float()
     if out is None:
         out = torch.empty((B, H, W), dtype=torch.int32, device=prob.device)
+    else:
+        _lib.require(out, torch.int32, shape=(B, H, W), name="argmax_2d: out")
     rc = _lib.load().pcnn_argmax_2d(_lib.ptr(prob), B, H, W, C, _lib.ptr(out), _lib.stream_ptr(stream))
     _lib.check(rc, "argmax_2d")
     return out

@@ -205,6 +205,50 @@ class PoseStep:
                 self._fork_evs[k] = ev
         self._mid_covers_pre = False  # the mid event was recorded after the prefetch it follows was joined
         self._mid_waited = False      # this step's stream already waited for the previous step's mid event
+        self._packed = {}  # name -> (source tensor, its version, packed fp32 copy): see _packed_f32
+        self._check_buffers()
+
+    def _check_buffers(self):
+        """The primitives' argument contract on
+        everything the step hands them on every call: the weights, the
+        gradients and its own fixed buffers, once, here.  step() then calls
+        the primitives with checked=False; what arrives per minibatch (the
+        maps, the rois' inputs, points / symmetry) goes through wrappers that
+        check or normalise on every call."""
+        f32, i32 = torch.float32, torch.int32
+        w, D, K6, U = self.weights, self.D, 49 * self.Ch, self.y6.shape[1]
+        for name, shape in (("w6", (K6, U)), ("b6", (U,)), ("w7", (U, U)), ("b7", (U,)), ("w8", (U, D)), ("b8", (D,))):
+            _lib.require(getattr(w, name), f32, shape=shape, name=f"PoseStep: weights.{name}")
+            sharded = self.gshard is not None and name[0] == "w"  # this rank's row block
+            _lib.require(self.grads[name], f32, shape=(None, shape[1]) if sharded else shape,
+                         name=f"PoseStep: grads[{name!r}]")
+        for name, shape in (("y6", (CAP, U)), ("y7", (CAP, U)), ("dy7", (CAP, U)), ("dy6", (CAP, U)), ("y8", (CAP, D)),
+                            ("t8", (CAP, D)), ("pred", (CAP, D)), ("diff", (CAP, D)), ("dy8", (CAP, D)),
+                            ("dx", (CAP, K6)), ("loss", (1,)), ("one", (1,))):
+            _lib.require(getattr(self, name), f32, shape=shape, name=f"PoseStep: {name}")
+        if self.drop6 is not None:
+            for name in ("drop6", "drop7"):
+                _lib.require(getattr(self, name), torch.uint8, shape=(CAP, U), name=f"PoseStep: {name}")
+            _lib.require_counter(self.drop_step, "PoseStep: drop_step", torch.int64)
+        _lib.require_counter(self.norm_rows, "PoseStep: norm_rows")
+        for st in self._sets:
+            h = st["hough"]
+            for name, dt, shape in (("box", f32, (CAP, 7)), ("pose", f32, (CAP, 7)), ("target", f32, (CAP, D)),
+                                    ("weight", f32, (CAP, D)), ("domain", i32, (CAP,)), ("num_rois", i32, (2,))):
+                _lib.require(h[name], dt, shape=shape, name=f"PoseStep: hough[{name!r}]")
+            _lib.require(st["pool"], f32, shape=(CAP, 7, 7, self.Ch), name="PoseStep: pool")
+
+    def _packed_f32(self, name, t):
+        """`t` itself when it is packed fp32 (the well-formed path: attribute
+        reads only), else a packed fp32 copy, made once per source tensor and
+        version -- model points / symmetry loaded as float64 (np.loadtxt) or
+        sliced out of a wider table; the step's primitives refuse those."""
+        if t.dtype == torch.float32 and t.is_contiguous():
+            return t
+        hit = self._packed.get(name)
+        if hit is None or hit[0] is not t or hit[1] != t._version:
+            hit = self._packed[name] = (t, t._version, t.contiguous().float())
+        return hit[2]
 
     # ------------------------------------------------------------------
     def _t(self, name):
@@ -287,6 +331,7 @@ class PoseStep:
         (`stream` given: on that stream, already ordered after the vote)."""
         s = self._cur if s is None else s
         st = self._sets[s]
+        points, symmetry = self._packed_f32("points", points), self._packed_f32("symmetry", symmetry)
         if st["add_ws"] is None:
             st["add_ws"] = torch.empty(adl.workspace_bytes(CAP, self.C, points.shape[1]), dtype=torch.uint8,
                                        device=self.dev)
@@ -423,6 +468,7 @@ class PoseStep:
         return self.xchg
 
     def forward(self, conv4, conv5, points, symmetry):
+        points, symmetry = self._packed_f32("points", points), self._packed_f32("symmetry", symmetry)
         h = self.hough
         nr = h["num_rois"][1:2]  # output row count (incl. dummy row)
         w = self.weights
@@ -458,14 +504,16 @@ class PoseStep:
                 # the fc7 GEMM alone; its reduce runs inside the fc8 forward's
                 # staging, fc8's reduce inside the pose head's row pass
                 ws7 = self._timed_gemm("fc7_fwd", lambda: ph.gemm_partial(self.y6, w.w7, self.y7, bias=w.b7, act=1,
-                                                                          M_dev=nr, precision=self.prec))
+                                                                          M_dev=nr, precision=self.prec,
+                                                                          checked=False))
 
                 def fc8_head():
                     ph.fc8_fwd_fused(ws7, w.units, w.b7, self.y7, w.w8, act=1, drop=self.drop7,
-                                     drop_gen=g7.get("drop_gen"), M_dev=nr, **dk)
+                                     drop_gen=g7.get("drop_gen"), M_dev=nr, checked=False, **dk)
                     if gs is not None:
                         gs.send_input("w8", self.y7)
-                    ph.fc8_reduce_head_fwd(w.b8, w.units, h["weight"], self.y8, self.t8, self.pred, num_rois=nr)
+                    ph.fc8_reduce_head_fwd(w.b8, w.units, h["weight"], self.y8, self.t8, self.pred, num_rois=nr,
+                                           checked=False)
                 self._timed_gemm("fc8_fwd", fc8_head)
             else:
                 self._g("fc7_fwd", self.y6, w.w7, self.y7, bias=w.b7, act=1, M_dev=nr, drop=self.drop7, **dk, **g7)
@@ -484,7 +532,7 @@ class PoseStep:
             self.norm_rows.clamp_(min=1)
         with self._t("head_add_loss_fwd"):
             if not self.fuse_fc8:  # (fused: done with fc8's reduce)
-                ph.head_fwd(self.y8, h["weight"], self.t8, self.pred, num_rois=nr)
+                ph.head_fwd(self.y8, h["weight"], self.t8, self.pred, num_rois=nr, checked=False)
             if not st["prepped"]:  # forward() called without step()
                 self.add_prep(points, symmetry)
             if st["prepped"] == "side":
@@ -503,11 +551,11 @@ class PoseStep:
                 ev = self._arm_fork("loss")
                 adl.average_distance_loss_head_bwd(self.pred, h["target"], h["weight"], points, symmetry,
                                                    self.margin, self.t8, self.one, self.diff, self.dy8, st["add_ws"],
-                                                   num_rois=nr, loss_norm_rows_dev=self.norm_rows)
+                                                   num_rois=nr, loss_norm_rows_dev=self.norm_rows, checked=False)
                 self._fork_side(side, self._fork_taken(ev))
                 with torch.cuda.stream(side):
                     adl.average_distance_loss_total(CAP, self.C, points.shape[1], st["add_ws"], self.loss,
-                                                    num_rois=nr)
+                                                    num_rois=nr, checked=False)
                     if self.dist is not None:  # joined at the end of the step
                         self._pending["loss"] = self.dist.all_reduce(self.loss, async_op=True)
                 return self.loss
@@ -551,7 +599,7 @@ class PoseStep:
                 else:
                     # the bias sum first: a short launch ahead of the long dW GEMM, not
                     # a tail after it (fc6: it ran 44 us behind the dW, beside the pool bwd)
-                    ph.colsum(dY, g["b" + name[1:]], M_dev=nr)
+                    ph.colsum(dY, g["b" + name[1:]], M_dev=nr, checked=False)
                     self._g(f"fc{name[1:]}_dw", X, dY, g[name], a_trans=1, K_dev=nr, M=M, N=N, K=K_loc)
 
         # the fused loss tail already forked the side stream right after dY8
@@ -564,7 +612,7 @@ class PoseStep:
                 # average_distance_loss_grad (top_diff[0] * bottom_diff) folded into
                 # the head backward: one pass over the (R, 4C) rows instead of two
                 ph.head_bwd(self.diff, self.t8, h["weight"], self.pred, self.dy8, num_rois=nr,
-                            d_pred_scale=self.one)
+                            d_pred_scale=self.one, checked=False)
         self._head_bwd_done = False
         if self.prefetch_at == "bwd":
             self._prefetch()
@@ -575,7 +623,7 @@ class PoseStep:
         with self._t("gemm_fc8_fc7_dx"):
             if self.fuse_fc8:
                 self._timed_gemm("fc8_dx", lambda: ph.fc8_dx(self.dy8, w.w8, self.dy7, mask=self.y7, M_dev=nr,
-                                                             precision=self.prec, **dk))
+                                                             precision=self.prec, checked=False, **dk))
             else:
                 self._g("fc8_dx", self.dy8, w.w8, self.dy7, b_trans=1, mask=self.y7, M_dev=nr, **dk)
         ev = self._fork_taken(ev)
@@ -627,7 +675,7 @@ class PoseStep:
     def _g(self, name, A, B, C, **kw):
         """One FC GEMM at the step's precision, bracketed by HIP events on the
         stream it is launched on when gemm_timer is set."""
-        self._timed_gemm(name, lambda: ph.gemm(A, B, C, precision=self.prec, **kw))
+        self._timed_gemm(name, lambda: ph.gemm(A, B, C, precision=self.prec, checked=False, **kw))
         return C
 
     def _timed_gemm(self, name, launch):
@@ -653,6 +701,9 @@ class PoseStep:
         the RoI pools read the network's label / vertex / conv maps), so every
         output is the unpipelined step's, bit for bit.  A call whose inputs
         were not prefetched runs its own front chain first."""
+        return self._step(inputs, next_inputs)
+
+    def _step(self, inputs, next_inputs):
         if self.pipeline:
             return self._step_pipelined(inputs, next_inputs)
         if next_inputs is not None:

@@ -39,6 +39,13 @@ def roi_pool(bottom_data, bottom_rois, pooled_height, pooled_width, spatial_scal
         arg = torch.empty(shape, dtype=torch.int32, device=data.device)
     else:
         top, arg = out
+        _lib.require(top, torch.float32, shape=(None,) + shape[1:], name="roi_pool: out[0] (top)")
+        _lib.require(arg, torch.int32, shape=(None,) + shape[1:], name="roi_pool: out[1] (argmax)")
+        if top.shape[0] < R or arg.shape[0] < R:  # (capacity buffers may hold more rows than there are rois)
+            raise ValueError(f"roi_pool: out needs {R} rows, got {top.shape[0]} and {arg.shape[0]}")
+    _lib.require_counter(num_rois, "roi_pool: num_rois")
+    if stride < 5:
+        raise ValueError(f"roi_pool: rois rows need at least 5 columns, got {stride}")
     lib = _lib.load()
     if R == 0:  # nothing to pool; a zero-row tensor has no pointer for the library's argument check
         return top, arg
@@ -77,6 +84,14 @@ def roi_pool_pair(data_a, scale_a, data_b, scale_b, rois, pooled_height, pooled_
     top, arg_a, arg_b = out
     if arg_a.dtype != arg_b.dtype or arg_a.dtype not in (torch.int16, torch.int32):
         raise ValueError("argmax tensors must both be int32 (flat index) or int16 (pixel index)")
+    for i, t in enumerate((top, arg_a, arg_b)):
+        _lib.require(t, torch.float32 if i == 0 else arg_a.dtype, shape=(None,) + shape[1:],
+                     name=f"roi_pool_pair: out[{i}]")
+        if t.shape[0] < R:  # (capacity buffers may hold more rows than there are rois)
+            raise ValueError(f"roi_pool_pair: out[{i}] needs {R} rows, got {t.shape[0]}")
+    _lib.require_counter(num_rois, "roi_pool_pair: num_rois")
+    if stride < 5:
+        raise ValueError(f"roi_pool_pair: rois rows need at least 5 columns, got {stride}")
     if R == 0:  # as roi_pool
         return top, arg_a, arg_b
     fn = _lib.load().pcnn_roi_pool_fwd_pair_px if arg_a.dtype == torch.int16 else _lib.load().pcnn_roi_pool_fwd_pair
@@ -90,16 +105,33 @@ def roi_pool_pair(data_a, scale_a, data_b, scale_b, rois, pooled_height, pooled_
 def roi_pool_grad(bottom_data, bottom_rois, argmax, grad, pooled_height, pooled_width, spatial_scale,
                   pool_channel=0, name=None, num_rois=None, layout=0, out=None, batch_base=0):
     _lib.require_gpu(bottom_data, bottom_rois, argmax, grad)
+    if bottom_data.dim() != 4 or bottom_rois.dim() != 2:
+        raise ValueError("data must be 4-dimensional and rois 2-dimensional")
     rois = bottom_rois.contiguous().float()
     if layout == 0:
         B, H, W, C = bottom_data.shape
     else:
         B, C, H, W = bottom_data.shape
     R, stride = rois.shape
+    if stride < 5:
+        raise ValueError(f"roi_pool_grad: rois rows need at least 5 columns, got {stride}")
+    Co = 1 if pool_channel else C
+    n_top = R * int(pooled_height) * int(pooled_width) * Co
+    if argmax.dtype.is_floating_point or argmax.dtype.is_complex or argmax.dtype == torch.bool:
+        raise ValueError(f"roi_pool_grad: argmax must be an integer tensor, got {argmax.dtype}")
+    px = argmax.dtype == torch.int16  # pixel-index argmax of roi_pool_pair(pixel_argmax=True)
+    # the reference op's argmax is int32 (roi_pooling_op.cc:47); any other integer width is converted
+    argmax = argmax.contiguous() if px else argmax.contiguous().to(torch.int32)
+    grad = grad.contiguous().float()
+    if argmax.numel() != n_top or grad.numel() != n_top:
+        raise ValueError(f"roi_pool_grad: argmax and grad must have {n_top} elements "
+                         f"(R x pooled_height x pooled_width x channels), got {argmax.numel()} and {grad.numel()}")
+    _lib.require_counter(num_rois, "roi_pool_grad: num_rois")
+    if out is not None:
+        _lib.require(out, torch.float32, shape=tuple(bottom_data.shape), name="roi_pool_grad: out")
     lib = _lib.load()
     ws = _lib.workspace(lib.pcnn_roi_pool_bwd_workspace_size(B, R), bottom_data.device, "roi_bwd")
     dd = out if out is not None else torch.empty(bottom_data.shape, dtype=torch.float32, device=bottom_data.device)
-    px = argmax.dtype == torch.int16  # pixel-index argmax of roi_pool_pair(pixel_argmax=True)
     if R == 0:
         # zero-row tensors have no pointer for the library's argument check; with R_cap = 0 the
         # library reads none of the three and writes the all-zero gradient, so the workspace stands in
@@ -107,12 +139,12 @@ def roi_pool_grad(bottom_data, bottom_rois, argmax, grad, pooled_height, pooled_
     if px:
         if layout != 0 or pool_channel:
             raise ValueError("a pixel-index argmax needs NHWC data and pool_channel 0")
-        rc = lib.pcnn_roi_pool_bwd_px(_lib.ptr(grad.contiguous()), _lib.ptr(argmax.contiguous()), B, H, W, C,
+        rc = lib.pcnn_roi_pool_bwd_px(_lib.ptr(grad), _lib.ptr(argmax), B, H, W, C,
                                       _lib.ptr(rois), R, stride, int(batch_base), _lib.ptr(num_rois),
                                       float(spatial_scale), int(pooled_height), int(pooled_width), _lib.ptr(dd),
                                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
     else:
-        rc = lib.pcnn_roi_pool_bwd(_lib.ptr(grad.contiguous()), _lib.ptr(argmax.contiguous()), B, H, W, C, layout,
+        rc = lib.pcnn_roi_pool_bwd(_lib.ptr(grad), _lib.ptr(argmax), B, H, W, C, layout,
                                    _lib.ptr(rois), R, stride, int(batch_base), _lib.ptr(num_rois),
                                    float(spatial_scale), int(pooled_height), int(pooled_width), int(pool_channel),
                                    _lib.ptr(dd), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())

@@ -27,6 +27,14 @@ def _f(t):
     return t.contiguous().float()
 
 
+def _records(what, records, counts):
+    """energy_records' outputs as the record kernels read them: packed (N, stride, 6) float32 and (N) int32."""
+    if records.dim() != 3 or records.shape[2] != 6:
+        raise ValueError(f"{what}: records must be (N, stride, 6), got {tuple(records.shape)}")
+    return records.contiguous().float(), _lib.require(counts.contiguous().to(torch.int32), torch.int32,
+                                                      shape=(records.shape[0],), name=f"{what}: counts")
+
+
 def live_vertices(depth, label, obj_ids, factor, camera, stream=None):
     """df::backproject of the depth masked to each object (synthesize.cpp:2140-2160)."""
     _lib.require_gpu(depth, label)
@@ -46,7 +54,7 @@ def icp(live, pred_vertices, pred_normals, camera, depth_range=(0.25, 6.0), max_
         live_index=None, pose_in=None, return_systems=False, stream=None):
     """df::icp for N problems (one per row of pred_vertices (N,H,W,4)).
     Returns (update (N,7), pose_out (N,7) = update * pose_in or None[, systems (N,it,28)])."""
-    _lib.require_gpu(live, pred_vertices, pred_normals)
+    _lib.require_gpu(live, pred_vertices, pred_normals, pose_in)
     pv, pn, lv = _f(pred_vertices), _f(pred_normals), _f(live)
     N, H, W = pv.shape[0], pv.shape[1], pv.shape[2]
     if pv.shape != (N, H, W, 4) or pn.shape != (N, H, W, 4) or lv.shape[1:] != (H, W, 3):
@@ -83,7 +91,7 @@ def icp(live, pred_vertices, pred_normals, camera, depth_range=(0.25, 6.0), max_
 def icp_center(live, label, obj_ids, vertmap, pred_vertices, pred_normals, max_error=0.01, pose_in=None,
                stream=None):
     """Translation re-centring of solveICP (synthesize.cpp:2163-2219) for L objects."""
-    _lib.require_gpu(live, label, vertmap, pred_vertices, pred_normals)
+    _lib.require_gpu(live, label, vertmap, pred_vertices, pred_normals, pose_in)
     lv, vm, pv, pn = _f(live), _f(vertmap), _f(pred_vertices), _f(pred_normals)
     L_, H, W = lv.shape[0], lv.shape[1], lv.shape[2]
     obj = torch.as_tensor(obj_ids).to(device=lv.device, dtype=torch.int32).contiguous()
@@ -188,6 +196,7 @@ def pose_energy_records(records, counts, poses, pose_prob, depth_range=(0.25, 6.
     (energy_records): one 1024-thread workgroup per pose, the same summation
     as nelder_mead_device's evaluations."""
     _lib.require_gpu(records, counts, poses)
+    records, counts = _records("pose_energy_records", records, counts)
     P = _f(poses)
     K = P.shape[0]
     pp = torch.as_tensor(pose_prob).to(device=records.device, dtype=torch.int32).contiguous()
@@ -223,6 +232,7 @@ def nelder_mead_device(records, counts, x0, lb, ub, max_eval, depth_range=(0.25,
         force_path = int(os.environ.get("PCNN_NM_PATH", "0") or 0)
     if force_path not in NM_PATHS:
         raise ValueError(f"nelder_mead_device: force_path in {sorted(NM_PATHS)}")
+    records, counts = _records("nelder_mead_device", records, counts)
     dev = records.device
     d64 = dict(dtype=torch.float64, device=dev)
     x0_, lb_, ub_ = (torch.as_tensor(a).to(**d64).contiguous() for a in (x0, lb, ub))

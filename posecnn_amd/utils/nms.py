@@ -25,15 +25,25 @@ def _run(dets, thresh, num_rois=None, poses_init=None, poses_pred=None, keep=Non
     if stride < 7:
         raise ValueError("nms: rows are [b, cls, x1, y1, x2, y2, score]")
     dev = d.device
+    _lib.require_counter(num_rois, "nms: num_rois")
+    if keep is not None:
+        _lib.require(keep, torch.int32, shape=(max(R, 1),), name="nms: keep")
     keep = keep if keep is not None else torch.empty((max(R, 1),), dtype=torch.int32, device=dev)
     num_keep = torch.zeros((1,), dtype=torch.int32, device=dev)
     rois_out = poses_out = None
     pi = pp = None
     pred_dim = 0
     if poses_init is not None:
+        _lib.require_gpu(poses_init, poses_pred)
         pi = poses_init.contiguous().float()
         pp = poses_pred.contiguous().float() if poses_pred is not None else None
+        if pi.dim() != 2 or pi.shape[0] < R or pi.shape[1] != 7 or (pp is not None and (pp.dim() != 2 or
+                                                                                       pp.shape[0] < R)):
+            raise ValueError(f"nms: poses_init must be ({R}, 7) and poses_pred ({R}, 4C)")
         pred_dim = pp.shape[1] if pp is not None else 0
+        if out is not None:
+            for i, t in enumerate(out):
+                _lib.require(t, torch.float32, shape=(max(R, 1), 7), name=f"nms_combine: out[{i}]")
         rois_out, poses_out = out if out is not None else (torch.zeros((max(R, 1), 7), device=dev),
                                                             torch.zeros((max(R, 1), 7), device=dev))
     rc = _lib.load().pcnn_box_nms(_lib.ptr(d), R, stride, _lib.ptr(num_rois), float(thresh), _lib.ptr(keep),

@@ -30,8 +30,12 @@ def vertex_pred_compact(feat, weights, biases, label, out=None, stream=None):
     C = w.shape[1] // 3
     feat = feat.contiguous().float()
     lab = label.contiguous().to(torch.int32)
+    if tuple(label.shape) != (B, H, W):
+        raise ValueError(f"label must be {(B, H, W)}, got {tuple(label.shape)}")
     if out is None:
         out = torch.empty((B, H, W, 3), dtype=torch.float32, device=feat.device)
+    else:
+        _lib.require(out, torch.float32, shape=(B, H, W, 3), name="vertex_pred_compact: out")
     rc = _lib.load().pcnn_vertex_pred_compact(_lib.ptr(feat), _lib.ptr(w), _lib.ptr(biases.contiguous().float()),
                                               _lib.ptr(lab), B, H, W, K, C, _lib.ptr(out), _lib.stream_ptr(stream))
     _lib.check(rc, "vertex_pred_compact")
