@@ -8,7 +8,7 @@
 // 6: the backward of the class-compact vertex_pred layer (pcnn_vertex_pred_compact_bwd and its two queries)
 // 7: the upscore layers (pcnn_upscore_fwd, pcnn_upscore_bwd, pcnn_upscore_compact_fwd, pcnn_upscore_compact_bwd
 //    and the two workspace queries)
-extern "C" int pcnn_abi_version(void) { return 7; }
+extern "C" int pcnn_abi_version(void) { return 8; }
 
 extern "C" const char* pcnn_strerror(int code) {
   switch (code) {

@@ -3,15 +3,17 @@ libposecnn_hip.so (csrc/render.hip): the role of the reference's OpenGL pass
 (lib/synthesize/synthesize.cpp:2103-2139 with the canonicalVerts.* and
 vertsAndNorms.* shaders of lib/kinect_fusion/shaders).
 
-Mesh(vertices, faces, normals=None)       a triangle mesh with vertex normals
+Mesh(vertices, faces, normals=None,       a triangle mesh with vertex normals
+     colors=None)                          and vertex colours
 load_obj(path)                             -> Mesh (Wavefront v / vn / f lines)
 MeshRenderer(meshes, H, W, camera, ...)    solve_icp's `render`: __call__(obj, pose)
                                            and render_many(objs, poses) ->
                                            (vertmap, pred_vertices, pred_normals)
 
-No texture, colour or lighting, one object per image (scene.py renders
-several into one image); the geometry rules are at the top of csrc/render.hip
-and in DESIGN.md.
+No texture, colour or lighting here, one object per image (scene.py renders
+several into one image, image.py adds the lit colour picture of a scene from
+the meshes' vertex colours); the geometry rules are at the top of
+csrc/render.hip and in DESIGN.md.
 """
 import numpy as np
 import torch
@@ -34,9 +36,12 @@ def vertex_normals(vertices, faces):
 
 class Mesh:
     """vertices (V,3) float32 in the model frame, faces (F,3) int32 vertex
-    indices, normals (V,3) float32 (computed, area-weighted, when None)."""
+    indices, normals (V,3) float32 (computed, area-weighted, when None),
+    colors (V,3) float32 RGB in [0, 1] for the lit renderer (image.py), a
+    mid-grey 0.5 when None (the reference's own fallback for a mesh without
+    colours is a debug red)."""
 
-    def __init__(self, vertices, faces, normals=None):
+    def __init__(self, vertices, faces, normals=None, colors=None):
         self.vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
         V = len(self.vertices)
@@ -49,14 +54,21 @@ class Mesh:
         self.normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
         if len(self.normals) != V:
             raise ValueError("Mesh: one normal per vertex")
+        if colors is None:
+            colors = np.full((V, 3), 0.5, np.float32)
+        self.colors = np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+        if len(self.colors) != V:
+            raise ValueError("Mesh: one colour per vertex")
 
 
 def load_obj(path):
     """A small Wavefront reader: `v`, `vn` and `f` lines, the face forms i,
     i/j, i/j/k and i//k, negative (relative) indices, polygons fan-triangulated.
     Normals are taken per position index (the last face corner that names one
-    wins); when any vertex is left without one, all are computed."""
-    pos, nrm, faces, n_of = [], [], [], {}
+    wins); when any vertex is left without one, all are computed.  A file
+    whose every `v` line has the form `v x y z r g b` gives the vertex
+    colours; otherwise the colours are Mesh's default."""
+    pos, col, nrm, faces, n_of = [], [], [], [], {}
     with open(path) as fh:
         for line in fh:
             tok = line.split("#", 1)[0].split()
@@ -64,6 +76,8 @@ def load_obj(path):
                 continue
             if tok[0] == "v":
                 pos.append([float(x) for x in tok[1:4]])
+                if len(tok) == 7:
+                    col.append([float(x) for x in tok[4:7]])
             elif tok[0] == "vn":
                 nrm.append([float(x) for x in tok[1:4]])
             elif tok[0] == "f":
@@ -87,14 +101,16 @@ def load_obj(path):
     normals = None
     if pos and len(n_of) == len(pos):
         normals = np.asarray(nrm, np.float32)[[n_of[i] for i in range(len(pos))]]
-    return Mesh(np.asarray(pos, np.float32), np.asarray(faces, np.int32), normals)
+    colors = np.asarray(col, np.float32) if pos and len(col) == len(pos) else None
+    return Mesh(np.asarray(pos, np.float32), np.asarray(faces, np.int32), normals, colors)
 
 
 class PackedMeshes:
     """The view (H x W, camera = (fx, fy, px, py), znear, zfar) and the mesh
     set (dict obj_id -> Mesh) packed onto the device once, in the layout the
     C ABI takes: what MeshRenderer and SceneRenderer share.  slot[obj_id] is
-    the mesh's position in the set (the ABI's mesh_index)."""
+    the mesh's position in the set (the ABI's mesh_index); colors (V_total,3)
+    is packed like the vertices, for the lit renderer."""
 
     def __init__(self, meshes, H, W, camera, znear=0.25, zfar=6.0, device="cuda"):
         self.H, self.W = int(H), int(W)
@@ -113,6 +129,7 @@ class PackedMeshes:
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
         self.vertices = dev(np.concatenate([m.vertices for m in ms]))
         self.normals = dev(np.concatenate([m.normals for m in ms]))
+        self.colors = dev(np.concatenate([m.colors for m in ms]))
         self.faces = dev(np.concatenate([m.faces for m in ms]))
         self.vert_offset, self.face_offset = dev(voff), dev(foff)
 

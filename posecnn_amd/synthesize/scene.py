@@ -11,8 +11,9 @@ sample_scenes(B, classes, seed, ...)       the reference's scene sampling
 make_scene_frames(renderer, B, ...)        frames in synth.make_frames' layout,
                                            as device tensors
 
-Narrowings: no colour, texture or lighting (label, depth, vertex map and vote
-targets only); no `box` from the model point cloud (train_net.py:236-252); the
+Narrowings: the ground truth only (label, depth, vertex map and vote targets;
+image.py renders the lit colour picture and builds the input blob, without a
+texture path); no `box` from the model point cloud (train_net.py:236-252); the
 depth is metric float32, not the uint16 factor_depth encoding (:205-207).  The
 geometry rules are at the top of csrc/render.hip, the scene rules at the top
 of csrc/render_scene.hip and in DESIGN.md "Scene renderer".
@@ -184,7 +185,7 @@ def sample_scenes(B, classes, seed, image_offset=0, num_objects=(5, 8), tnear=0.
 
 def make_scene_frames(renderer, B, classes=None, seed=0, image_offset=0, num_objects=(5, 8), tnear=0.5, tfar=2.0,
                       min_dist=0.2, min_pixels=800, num_classes=None, full_vertex=False, w_inside=10.0, voxel=None,
-                      max_attempts=100):
+                      max_attempts=100, render=None, extra=()):
     """B training frames rendered by `renderer` (a SceneRenderer whose mesh
     keys are the class ids), in the layout of synth.make_frames but as device
     tensors: label (B,H,W) int32, vertex3 (B,H,W,3) the class-compact vote
@@ -199,7 +200,13 @@ def make_scene_frames(renderer, B, classes=None, seed=0, image_offset=0, num_obj
     the frames depend on the global image index alone.  This convenience
     renders only the images still rejected (an image's maps do not depend on
     its batch), reads their `visible` back once per attempt and so syncs with
-    the device; SceneRenderer.render does not."""
+    the device; SceneRenderer.render does not.
+
+    render(global image indices and scene_offset on the host, then
+    scene_offset, mesh_index, class_id, poses on the device) -> dict replaces
+    renderer.render(..., return_inst_id=False) for the attempts' draws, and each per-image map of its result named in `extra` is carried
+    through the rejection loop into the frames under its own name (image.py's
+    `color`: an accepted scene is not rendered twice)."""
     classes = sorted(renderer.slot) if classes is None else [int(c) for c in classes]
     C = int(num_classes) if num_classes is not None else max(renderer.slot) + 1
     dev, H, W = renderer.device, renderer.H, renderer.W
@@ -207,6 +214,7 @@ def make_scene_frames(renderer, B, classes=None, seed=0, image_offset=0, num_obj
     label = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     vertex3 = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    more = {}  # the maps named in `extra`, allocated from the first attempt's
     scene = [None] * B  # per image: (class ids, poses, visible) of its accepted draw
     todo, attempt = np.arange(B), 0
     while todo.size:
@@ -218,13 +226,20 @@ def make_scene_frames(renderer, B, classes=None, seed=0, image_offset=0, num_obj
         off = np.concatenate([[0], np.cumsum([len(c) for _, c, _ in drawn])]).astype(np.int32)
         cls = np.concatenate([c for _, c, _ in drawn])
         slots = np.array([renderer.slot[int(c)] for c in cls], np.int32)
-        out = renderer.render(t(off), t(slots), t(cls), t(np.concatenate([p for _, _, p in drawn])),
-                              return_inst_id=False)
+        poses = t(np.concatenate([p for _, _, p in drawn]))
+        if render is None:
+            out = renderer.render(t(off), t(slots), t(cls), poses, return_inst_id=False)
+        else:
+            out = render(todo + image_offset, off, t(off), t(slots), t(cls), poses)
         visible = out["visible"].cpu().numpy()
         ok = np.array([visible[off[j]:off[j + 1]].min() >= min_pixels for j in range(len(todo))])
         if ok.any():
             src, dst = t(np.flatnonzero(ok)), t(todo[ok])
             label[dst], depth[dst], vertex3[dst] = out["label"][src], out["depth"][src], out["vertex3"][src]
+            for k in extra:
+                if k not in more:
+                    more[k] = torch.empty((B,) + tuple(out[k].shape[1:]), dtype=out[k].dtype, device=dev)
+                more[k][dst] = out[k][src]
             for j in np.flatnonzero(ok):
                 scene[todo[j]] = (drawn[j][1], drawn[j][2], visible[off[j]:off[j + 1]])
         todo, attempt = todo[~ok], attempt + 1
@@ -242,6 +257,7 @@ def make_scene_frames(renderer, B, classes=None, seed=0, image_offset=0, num_obj
     frames = dict(label=label, vertex3=vertex3, depth=depth.unsqueeze(-1), meta=t(synth.make_meta(K, B, voxel)),
                   gt=t(gt), extents=t(extents), K=t(K.astype(np.float32)),
                   visible=t(np.concatenate([v for _, _, v in scene]).astype(np.int32)), scene_offset=t(off))
+    frames.update(more)
     if full_vertex:
         frames["vertex"], frames["vertex_weights"] = expand(label, vertex3, C, w_inside)
     return frames
