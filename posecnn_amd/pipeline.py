@@ -206,6 +206,7 @@ class PoseStep:
         self._mid_covers_pre = False  # the mid event was recorded after the prefetch it follows was joined
         self._mid_waited = False      # this step's stream already waited for the previous step's mid event
         self._packed = {}  # name -> (source tensor, its version, packed fp32 copy): see _packed_f32
+        self.optim = None  # make_optimizer(): the momentum-SGD plan over the weights and self.grads, and its settings
         self._check_buffers()
 
     def _check_buffers(self):
@@ -277,6 +278,46 @@ class PoseStep:
             if st is not None:
                 cur.wait_stream(st)
         self._side_pending = False
+
+    def make_optimizer(self, lr=0.001, momentum=0.9, weight_reg=1e-4, gamma=0.1, stepsize=30000):
+        """The reference's train_op for the pose head (optim.py; the defaults
+        are lib/fcn/config.py:54,99-102): one fused momentum-SGD plan over
+        weights.w6 .. b8 and self.grads, both persistent buffers, so the table
+        is built once, here.  All six tensors are regularised (network.py:
+        417-419).  Returns the plan: step_dev, reg_loss (the L2 term of the
+        reference's reported loss, on the weights the step's forward used) and
+        lr_used are device tensors apply_gradients() writes.  The image-sharded
+        step is refused: each rank holds a row block of the weight gradients,
+        and the update of a block needs an all-gather of the updated rows."""
+        if self.dist is not None:
+            raise NotImplementedError("PoseStep.make_optimizer: the image-sharded step (dist set) has no weight "
+                                      "update yet: its gradients are per-rank row blocks")
+        from . import optim
+        names = ("w6", "b6", "w7", "b7", "w8", "b8")
+        params = [getattr(self.weights, k) for k in names]
+        grads = [self.grads[k] for k in names]
+        plan = optim.momentum_sgd_plan(params, grads, [torch.zeros_like(p) for p in params])
+        self.optim = (plan, dict(lr=lr, momentum=momentum, weight_reg=weight_reg, gamma=gamma, stepsize=stepsize))
+        return plan
+
+    def apply_gradients(self):
+        """The weight update after step(): join(), then one fused momentum-SGD
+        call on the caller's current stream over the plan of make_optimizer().
+        No sync; capturable.
+
+        A loop that applies the gradients every step gives up the overlap
+        defer_side_join buys: the next step's fc6 forward needs the new w6, so
+        it cannot start beside this step's fc6 dW -- the join here orders the
+        weight-gradient stream first.  The prefetch of the next minibatch's
+        vote and RoI pools reads no weight and overlaps as before."""
+        if self.dist is not None:
+            raise NotImplementedError("PoseStep.apply_gradients: the image-sharded step (dist set) has no weight "
+                                      "update yet")
+        if self.optim is None:
+            raise _lib.PcnnError("PoseStep.apply_gradients: call make_optimizer() first")
+        self.join()
+        plan, kw = self.optim
+        plan.apply(**kw)
 
     def _side_wait(self, ev_name, stream=None):
         """Deferred join: `stream` (default the current one) waits for the
