@@ -155,11 +155,7 @@ static int gemm_impl(int M, int N, int K, const float* A, const float* A2, int l
     PCNN_CHECK_LAUNCH();
     return PCNN_OK;
   }
-  // ragged edges: a KC operand whose K (or device-side K) is not a multiple of
-  // 4, or an NC operand whose row count is not -> element-wise edge loads
-  const bool a_kc = !a_trans, b_kc = b_trans;
-  const bool ragged = ((a_kc || b_kc) && (K % 4 != 0 || K_dev != nullptr)) || (!a_kc && M % 4 != 0) ||
-                      (!b_kc && N % 4 != 0);
+  const bool ragged = split_ragged(a_trans != 0, b_trans != 0, M, N, K, K_dev != nullptr);
   const SplitVariant v{a_trans != 0, b_trans != 0, ragged, A2 != nullptr, plan.gen};
   const hipEvent_t done_ev = reduce_after ? pcnn::take_done_event() : nullptr;
   if (precision == 2) launch_gemm_x6(g, v, st);

@@ -160,6 +160,15 @@ inline LaunchPlan plan_launch(int M, int N, int K, bool m_dynamic, int precision
   return p;
 }
 
+// Ragged edges of a split kernel's operands: a KC (k-contiguous) operand whose
+// K (or device-side K) is not a multiple of 4, or an NC (row-contiguous)
+// operand whose row count is not -> a float4 of a staging load may straddle
+// the operand's edge, and the kernel takes element-wise edge loads.
+inline bool split_ragged(bool a_trans, bool b_trans, int M, int N, int K, bool k_dynamic) {
+  const bool a_kc = !a_trans, b_kc = b_trans;
+  return ((a_kc || b_kc) && (K % 4 != 0 || k_dynamic)) || (!a_kc && M % 4 != 0) || (!b_kc && N % 4 != 0);
+}
+
 // Whether k_gemm_reduce follows the GEMM kernel: to sum split-K slabs when
 // the plan can split, or to apply dropout / the backward's 1 / keep.  (A
 // no-op launch is not free: queued behind a persistent GEMM on another stream
