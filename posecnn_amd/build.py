@@ -16,8 +16,8 @@ SOURCES = ["capi.hip", "hough_compact.hip", "hough_vote.hip", "hough_peak.hip", 
            "average_distance.hip", "backprojecting.hip", "pose_head.hip", "gemm.hip", "gemm_f32.hip", "gemm_x3.hip",
            "gemm_x6.hip", "box_nms.hip", "label_producer.hip", "icp.hip", "dropout.hip", "pose2d.hip", "gemm_tp.hip",
            "render.hip", "render_scene.hip", "render_lit.hip", "seg_loss.hip", "vertex_pred_bwd.hip", "fc8_fused.hip", "upscore.hip",
-           "momentum.hip", "pose_eval.hip"]
-HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", h) for h in ("posecnn_hip.h", "posecnn_image.h", "posecnn_train.h", "posecnn_eval.h")]
+           "momentum.hip", "pose_eval.hip", "neck.hip"]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", h) for h in ("posecnn_hip.h", "posecnn_image.h", "posecnn_train.h", "posecnn_eval.h", "posecnn_neck.h")]
 # -ffp-contract=off: the parity arithmetic rounds every float op separately
 # (reference semantics restated by oracle/); MFMA kernels are unaffected.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
