@@ -41,6 +41,11 @@ both branches):
 
     EmbeddingNeck(in_channels=512, num_units=64, vertex_units=128, keep_prob=0.5, seed=0)(conv4_3, conv5_3)
         -> (add_score (B,h,w,num_units), add_score_vertex (B,h,w,vertex_units))
+
+and the backbone in front of that (posecnn_amd.backbone: the thirteen 3x3
+convs and four max-pools of vgg16_convs.py:80-97; forward only):
+
+    VGG16Convs(seed=0)(blob (B,H,W,3)) -> (conv4_3, conv5_3)
 """
 import torch
 from torch import nn
@@ -52,6 +57,7 @@ from . import losses
 from . import vertex_pred as vp
 from . import upscore as up
 from . import neck as nk
+from . import backbone as bb
 from . import pose_head as ph
 
 
@@ -416,6 +422,62 @@ class EmbeddingNeck(nn.Module):
             if v.shape != p.shape:
                 raise ValueError(f"{name}: expected shape {tuple(p.shape)}, got {tuple(v.shape)}")
             p.copy_(v)
+
+
+class _ConvVars(nn.Module):
+    """The variable pair of one conv layer under the reference's names (network.py:170, :183)."""
+
+    def __init__(self, cin, cout, generator):
+        super().__init__()
+        self.weights = nn.Parameter(ph.truncated_normal((3, 3, cin, cout), 0.001, generator, "cpu"),
+                                    requires_grad=False)
+        self.biases = nn.Parameter(torch.zeros(cout), requires_grad=False)
+
+
+class VGG16Convs(nn.Module):
+    """The backbone of vgg16_convs.py:80-97 over posecnn_amd.backbone: blob
+    (B,H,W,3) NHWC float32 -> (conv4_3 (B,ceil(H/8),ceil(W/8),512), conv5_3
+    (B,ceil(H/16),ceil(W/16),512)), the inputs of EmbeddingNeck (which wants
+    H and W multiples of 16).  Parameters are the reference's variables under
+    its names, conv1_1.weights (3,3,3,64) HWIO, conv1_1.biases (64), ...,
+    initialised as the reference does (truncated normal, stddev 0.001; zero
+    biases).  Forward only: the parameters are created with
+    requires_grad=False, and forward raises NotImplementedError rather than
+    hand back zero gradients if the input or a parameter requires grad."""
+
+    def __init__(self, seed=0):
+        super().__init__()
+        g = torch.Generator(device="cpu")
+        g.manual_seed(int(seed))
+        for name, cin, cout in bb.CONVS:
+            setattr(self, name, _ConvVars(cin, cout, g))
+
+    def params(self):
+        return {name: (getattr(self, name).weights, getattr(self, name).biases) for name, _, _ in bb.CONVS}
+
+    def forward(self, blob, keep=()):
+        needs = [n for n, p in self.named_parameters() if p.requires_grad]
+        if blob.requires_grad or needs:
+            what = "the input" if blob.requires_grad else needs[0]
+            raise NotImplementedError(f"VGG16Convs: {what} requires grad, but the backward of the 3x3 conv and the "
+                                      "max-pool is not built; detach the input and keep requires_grad=False")
+        with torch.no_grad():
+            return bb.vgg16_convs(blob, self.params(), keep=keep)
+
+    @torch.no_grad()
+    def load_reference(self, **layers):
+        """load_reference(conv1_1=(weights (3,3,3,64), biases (64)), ...): the
+        reference's variable pairs by layer name, any subset of the thirteen."""
+        known = {name: (cin, cout) for name, cin, cout in bb.CONVS}
+        for name, pair in layers.items():
+            if name not in known:
+                raise ValueError(f"load_reference: unknown layer {name}; expected one of {tuple(known)}")
+            mod = getattr(self, name)
+            for p, v, what in ((mod.weights, pair[0], "weights"), (mod.biases, pair[1], "biases")):
+                v = torch.as_tensor(v, dtype=torch.float32)
+                if v.shape != p.shape:
+                    raise ValueError(f"{name}.{what}: expected shape {tuple(p.shape)}, got {tuple(v.shape)}")
+                p.copy_(v)
 
 
 class AverageDistanceLoss(nn.Module):
