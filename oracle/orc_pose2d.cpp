@@ -183,7 +183,7 @@ int quartic_roots(const double* c, double* out) {
   for (int k = 0; k < 4; k++) { z[k] = w * bound; w *= seed; }
   auto pe = [&](cd x) { return (((x + a[3]) * x + a[2]) * x + a[1]) * x + a[0]; };
   // up to 200 sweeps, stopping at the first whose steps are all below 1e-9
-  // of their root (pose2d.hip stops at the same sweep)
+  // of their root (pose_ransac.h stops at the same sweep)
   for (int it = 0; it < 200; it++) {
     double mstep = 0;
     for (int k = 0; k < 4; k++) {
@@ -566,7 +566,7 @@ double det3(const double* m) {
 // The fixed summation tree of the GPU's 1024-thread workgroups (n <= 1024):
 // leaf i = 0.0 + x_i (0.0 past n); each 64-leaf wave folds by halving
 // (p_i += p_{i + off}, off = 32 .. 1), then the 16 wave sums fold the same way
-// (off = 8 .. 1) -- posecnn_amd/csrc/pose2d.hip tree_sum
+// (off = 8 .. 1) -- posecnn_amd/csrc/pose_ransac.h wave_fold / cross_fold
 template <class T, class F>
 T tree1024(F x, int n) {
   T p[1024];
@@ -624,7 +624,7 @@ V3 xform(const Pose& P, V3 p) {  // Hypothesis::transform
 }
 
 // sin / cos / acos from + - * / and sqrt only, so that the device computes
-// the same bits (posecnn_amd/csrc/pose2d.hip): quadrant reduction by a
+// the same bits (posecnn_amd/csrc/pose3d.hip): quadrant reduction by a
 // two-part pi/2, the fdlibm kernel polynomials; acos by the half-angle
 // identity and 6 Newton steps on asin
 void dsincos(double x, double& s, double& c) {

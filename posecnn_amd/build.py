@@ -14,7 +14,7 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libposecnn_hip.so")
 SOURCES = ["capi.hip", "hough_compact.hip", "hough_vote.hip", "hough_peak.hip", "hough_emit.hip", "roi_pooling.hip",
            "average_distance.hip", "backprojecting.hip", "pose_head.hip", "gemm.hip", "gemm_f32.hip", "gemm_x3.hip",
-           "gemm_x6.hip", "box_nms.hip", "label_producer.hip", "icp.hip", "dropout.hip", "pose2d.hip", "gemm_tp.hip",
+           "gemm_x6.hip", "box_nms.hip", "label_producer.hip", "icp.hip", "pose_search.hip", "dropout.hip", "pose2d.hip", "pose3d.hip", "gemm_tp.hip",
            "render.hip", "render_scene.hip", "render_lit.hip", "seg_loss.hip", "vertex_pred_bwd.hip", "fc8_fused.hip", "upscore.hip",
            "momentum.hip", "pose_eval.hip", "neck.hip", "backbone.hip"]
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", h) for h in ("posecnn_hip.h", "posecnn_image.h", "posecnn_train.h", "posecnn_eval.h", "posecnn_neck.h", "posecnn_backbone.h")]

@@ -26,35 +26,16 @@
 // reaches HBM and the host is never involved.
 //
 // Rendering (the OpenGL vertex / normal / canonical-coordinate maps of the
-// model at a pose, synthesize.cpp:2106-2137) and the NLopt Nelder-Mead pose
-// search (poseWithOpt, :2529-2573) are outside the path: the maps are inputs.
-#include "pcnn_common.h"
+// model at a pose, synthesize.cpp:2106-2137) is outside the path: the maps
+// are inputs.  The Nelder-Mead pose search (poseWithOpt, :2529-2573) runs on
+// the device too, over compacted records: pose_search.hip.
+#include "refine_common.h"
 
 namespace pcnn_refine {
 
-constexpr int kSeg = 2048;       // pixels per compaction / reduction block
-constexpr int kBlk = 256;        // threads of the per-pixel kernels
 constexpr int kSys = 28;         // 21 upper-triangle JTJ + 6 JTr + pixel count
 
-struct Quat { float w, x, y, z; };
 struct SE3 { Quat q; float t[3]; };
-
-// Eigen Quaternion::_transformVector (the point action of Sophus SO3)
-__device__ __forceinline__ void rotate(const Quat& q, float v0, float v1, float v2, float& o0, float& o1,
-                                       float& o2) {
-  float uv0 = q.y * v2 - q.z * v1;
-  float uv1 = q.z * v0 - q.x * v2;
-  float uv2 = q.x * v1 - q.y * v0;
-  uv0 = uv0 + uv0;
-  uv1 = uv1 + uv1;
-  uv2 = uv2 + uv2;
-  const float c0 = q.y * uv2 - q.z * uv1;
-  const float c1 = q.z * uv0 - q.x * uv2;
-  const float c2 = q.x * uv1 - q.y * uv0;
-  o0 = v0 + q.w * uv0 + c0;
-  o1 = v1 + q.w * uv1 + c1;
-  o2 = v2 + q.w * uv2 + c2;
-}
 
 // Sophus SE3 product a * b (quaternion renormalised by 2 / (1 + |q|^2))
 __device__ SE3 se3_mul(const SE3& a, const SE3& b) {
@@ -241,21 +222,6 @@ __device__ __forceinline__ float ordered_sum_strided(const float* __restrict__ p
       if (q0 + k < n) sum += v[k];
   }
   return sum;
-}
-
-__device__ __forceinline__ bool in_range(float z, float znear, float zfar) { return !(z < znear || z > zfar); }
-
-// Block-wide sum of an int (all threads call; result in every thread).
-template <int T>
-__device__ __forceinline__ int block_sum_int(int v, int* sh) {
-  v = pcnn::wave_sum(v);
-  if (pcnn::lane_id() == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < T / 64; w++) s += sh[w];
-  __syncthreads();
-  return s;
 }
 
 // ---------------------------------------------------------------------------
@@ -1171,666 +1137,4 @@ extern "C" int pcnn_icp_score(const float* live, const int32_t* label, int obj, 
   hipLaunchKernelGGL(k_score_choose, dim3(1), dim3(64), 0, st, score, cnt, nseg, J, choose);
   PCNN_CHECK_LAUNCH();
   return PCNN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Nelder-Mead on optEnergy, on the device (round 5).  solveICP's refinePose
-// (synthesize.cpp:2221-2250 -> poseWithOpt :2529-2573, NLopt LN_NELDERMEAD,
-// 7 parameters, bounds +-0.1 / +-0.01 / +-0.1, at most `iterations`
-// evaluations of optEnergy :2476-2526) used to run as Python generators with
-// one energy launch and one host read per simplex step.  Here:
-//   k_rec_count / k_rec_scatter  the object's pixels whose live vertex lies in
-//       the depth range (the pose-independent half of optEnergy's test), in
-//       raster order, as (rendered vertex, live vertex) records per problem;
-//   energy_rec  optEnergy of one pose over a problem's records by one
-//       1024-thread workgroup, a fixed summation order (thread-strided float
-//       sums, then a fixed wave / workgroup tree): k_energy_rec evaluates K
-//       poses, and k_nm runs whole searches, one workgroup per problem, with
-//       no host read until the end.  The search is the bounded Nelder-Mead of
-//       posecnn_amd/synthesize/icp.py nelder_mead_steps, operation for
-//       operation in double (NLopt is absent: its trajectory is unpinned), so
-//       the device search and the host search over k_energy_rec give the
-//       same bits.
-namespace pcnn_refine {
-
-constexpr int kNmThreads = 1024;
-constexpr int kNmDim = 7;
-
-__global__ void __launch_bounds__(kBlk) k_rec_count(const float* __restrict__ live_all, int n_live,
-                                                    const int32_t* __restrict__ label, int HW, float znear, float zfar,
-                                                    const int32_t* __restrict__ prob_obj,
-                                                    const int32_t* __restrict__ prob_live, int nseg,
-                                                    int32_t* __restrict__ segcnt) {
-  __shared__ int sh[kBlk / 64];
-  const int p = blockIdx.y, seg = blockIdx.x;
-  const int obj = prob_obj[p], li = prob_live[p];
-  const bool ok_live = li >= 0 && li < n_live;
-  const float* __restrict__ live = live_all + (ok_live ? (size_t)li * HW * 3 : 0);
-  int c = 0;
-  for (int i = threadIdx.x; i < kSeg; i += kBlk) {
-    const int j = seg * kSeg + i;
-    if (ok_live && j < HW && label[j] == obj) {
-      const float lz = live[(size_t)j * 3 + 2];
-      c += (lz > znear && lz < zfar) ? 1 : 0;  // :2514
-    }
-  }
-  c = block_sum_int<kBlk>(c, sh);
-  if (threadIdx.x == 0) segcnt[(size_t)p * nseg + seg] = c;
-}
-
-__global__ void __launch_bounds__(kBlk) k_rec_scatter(const float* __restrict__ live_all, int n_live,
-                                                      const int32_t* __restrict__ label,
-                                                      const float* __restrict__ pv_all, int HW, float znear,
-                                                      float zfar, const int32_t* __restrict__ prob_obj,
-                                                      const int32_t* __restrict__ prob_live, int nseg,
-                                                      const int32_t* __restrict__ segcnt, float* __restrict__ rec,
-                                                      int32_t* __restrict__ count) {
-  __shared__ int sh[kBlk / 64];
-  __shared__ int wc[kBlk / 64];
-  const int p = blockIdx.y, seg = blockIdx.x;
-  const int obj = prob_obj[p], li = prob_live[p];
-  const bool ok_live = li >= 0 && li < n_live;
-  const float* __restrict__ live = live_all + (ok_live ? (size_t)li * HW * 3 : 0);
-  const float* __restrict__ pv = pv_all + (size_t)p * HW * 4;
-  const int32_t* sc = segcnt + (size_t)p * nseg;
-  int o = 0, tot = 0;
-  for (int s = threadIdx.x; s < nseg; s += kBlk) {
-    o += s < seg ? sc[s] : 0;
-    tot += sc[s];
-  }
-  int off = block_sum_int<kBlk>(o, sh);
-  const int total = block_sum_int<kBlk>(tot, sh);
-  if (seg == 0 && threadIdx.x == 0) count[p] = total;
-  float* out = rec + (size_t)p * HW * 6;
-  const int wave = threadIdx.x >> 6;
-  for (int i0 = 0; i0 < kSeg; i0 += kBlk) {
-    const int j = seg * kSeg + i0 + threadIdx.x;
-    bool ok = false;
-    if (ok_live && j < HW && label[j] == obj) {
-      const float lz = live[(size_t)j * 3 + 2];
-      ok = lz > znear && lz < zfar;
-    }
-    const uint64_t m = __ballot(ok);
-    if (pcnn::lane_id() == 0) wc[wave] = __popcll(m);
-    __syncthreads();
-    int base = off;
-    for (int w = 0; w < wave; w++) base += wc[w];
-    if (ok) {
-      float* r = out + (size_t)(base + __popcll(m & pcnn::lanemask_lt())) * 6;
-      r[0] = pv[(size_t)j * 4 + 0];
-      r[1] = pv[(size_t)j * 4 + 1];
-      r[2] = pv[(size_t)j * 4 + 2];
-      r[3] = live[(size_t)j * 3 + 0];
-      r[4] = live[(size_t)j * 3 + 1];
-      r[5] = live[(size_t)j * 3 + 2];
-    }
-    for (int w = 0; w < kBlk / 64; w++) off += wc[w];
-    __syncthreads();
-  }
-}
-
-// optEnergy (:2476-2526) of pose P (float, quaternion normalised as
-// k_pose_energy does) over n records; every thread of a 1024-thread
-// workgroup calls it and gets the value
-// the record sums of virtual thread vt (of kNmThreads): records vt, vt +
-// kNmThreads, ... in order, four records' loads issued per pass (the loop
-// was bound by one record's load latency at a time; the order is unchanged)
-__device__ __forceinline__ void rec_sums(const float* __restrict__ r, int n, const Quat& q, const float (&P)[7],
-                                         float znear, float zfar, int vt, float& s, float& c) {
-  s = 0.f;
-  c = 0.f;
-  auto term = [&](const float* x) {
-    float p0, p1, p2;
-    rotate(q, x[0], x[1], x[2], p0, p1, p2);
-    p0 = p0 + P[4];
-    p1 = p1 + P[5];
-    p2 = p2 + P[6];
-    if (!isnan(p0) && !isnan(p1) && !isnan(p2) && p2 > znear && p2 < zfar) {  // :2514 (the live half: records)
-      const float dx = p0 - x[3], dy = p1 - x[4], dz = p2 - x[5];
-      s += sqrtf(dx * dx + dy * dy + dz * dz);
-      c += 1.f;
-    }
-  };
-  int i = vt;
-  for (; i + 3 * kNmThreads < n; i += 4 * kNmThreads) {
-    float v[4][6];
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-      for (int e = 0; e < 6; e++) v[u][e] = r[(size_t)(i + u * kNmThreads) * 6 + e];
-#pragma unroll
-    for (int u = 0; u < 4; u++) term(v[u]);
-  }
-  for (; i < n; i += kNmThreads) term(r + (size_t)i * 6);
-}
-
-__device__ __forceinline__ Quat rec_quat(const float (&P)[7]) {
-  const float qn = sqrtf(P[0] * P[0] + P[1] * P[1] + P[2] * P[2] + P[3] * P[3]);
-  return {P[0] / qn, P[1] / qn, P[2] / qn, P[3] / qn};
-}
-
-// optEnergy (:2476-2526) of pose P (float, quaternion normalised as
-// k_pose_energy does) over n records; every thread of a 1024-thread
-// workgroup calls it and gets the value
-__device__ float energy_rec(const float* __restrict__ r, int n, const float (&P)[7], float znear, float zfar,
-                            float* sh) {
-  const Quat q = rec_quat(P);
-  float s, c;
-  rec_sums(r, n, q, P, znear, zfar, threadIdx.x, s, c);
-  s = pcnn::wave_sum(s);
-  c = pcnn::wave_sum(c);
-  const int wave = threadIdx.x >> 6;
-  if (pcnn::lane_id() == 0) {
-    sh[2 * wave] = s;
-    sh[2 * wave + 1] = c;
-  }
-  __syncthreads();
-  float S = 0.f, Cn = 0.f;
-  for (int w = 0; w < kNmThreads / 64; w++) {
-    S += sh[2 * w];
-    Cn += sh[2 * w + 1];
-  }
-  __syncthreads();
-  return Cn > 0.f ? S / Cn : 0.f;  // distance /= c (:2520-2521)
-}
-
-__global__ void __launch_bounds__(kNmThreads) k_energy_rec(const float* __restrict__ rec,
-                                                           const int32_t* __restrict__ count, int stride,
-                                                           const float* __restrict__ poses,
-                                                           const int32_t* __restrict__ pose_prob, float znear,
-                                                           float zfar, float* __restrict__ energy) {
-  __shared__ float sh[2 * kNmThreads / 64];
-  const int k = blockIdx.x;
-  const int p = pose_prob[k];
-  float P[7];
-  for (int e = 0; e < 7; e++) P[e] = poses[(size_t)k * 7 + e];
-  const float v = energy_rec(rec + (size_t)p * stride * 6, count[p], P, znear, zfar, sh);
-  if (threadIdx.x == 0) energy[k] = v;
-}
-
-// Bounded Nelder-Mead (icp.py nelder_mead_steps, in its operation order):
-// simplex x0 + step_i e_i with step = min(0.25 (ub - lb), 0.75 (ub - x0),
-// 0.75 (x0 - lb)); each iteration a stable sort, the centroid of the best n
-// (a sequential sum / n), reflection, expansion, contraction (outside /
-// inside), shrink toward the best; trial points clamped to the bounds; at
-// most max_eval evaluations.  One workgroup per problem: thread 0 keeps the
-// simplex in LDS, every thread evaluates.
-// Arrive-and-wait of the G workgroups of one problem on its counter (thread 0
-// of each): release the workgroup's partial sums, wait until every workgroup
-// of the problem has arrived for this evaluation.  Bounded: a wait that never
-// completes (not expected: the launch is cooperative) gives up and raises the
-// problem's failure flag; a workgroup waiting while the flag is up gives up at
-// once.  A workgroup whose wait fails leaves the search (the caller checks
-// s_fail after its barrier), so every workgroup of the problem stops at its
-// next barrier instead of running on with sums that were never written, and
-// the problem reports nev = -1.
-__device__ __forceinline__ bool coop_arrive_wait(uint32_t* bar, uint32_t target, uint32_t* fail) {
-  __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  uint32_t cur = __hip_atomic_load(bar, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-  for (int it = 0; cur < target && it < (1 << 24); it++) {
-    if (__hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
-    __builtin_amdgcn_s_sleep(2);
-    cur = __hip_atomic_load(bar, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (cur >= target) return true;
-  __hip_atomic_fetch_or(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return false;
-}
-
-// nev reported by workgroup 0 of problem p: -1 when a cross-workgroup wait of
-// the problem gave up (its own or another workgroup's: results invalid)
-__device__ __forceinline__ int nm_report(int nev, int s_fail, const uint32_t* fail, int p) {
-  if (s_fail) return -1;
-  if (fail && __hip_atomic_load(fail + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return -1;
-  return nev;
-}
-
-// G workgroups per problem (G = 1: one 1024-thread workgroup; G > 1: the
-// 1024 "virtual threads" of optEnergy's reduction split over G workgroups of
-// kNmThreads / G, each running the same search).  Every evaluation's record
-// sums are those of energy_rec -- virtual thread v sums records v, v + 1024,
-// ... in order, each 64 of them fold by the same butterfly, the 16 wave sums
-// add in order -- so the value is identical for every G; with G > 1 the wave
-// sums cross workgroups through `part` (double-buffered by evaluation
-// parity) and one arrive-and-wait per evaluation on the problem's counter.
-template <int G>
-__global__ void __launch_bounds__(kNmThreads / G) k_nm(const float* __restrict__ rec,
-                                                       const int32_t* __restrict__ count, int stride,
-                                                       const double* __restrict__ x0_all,
-                                                       const double* __restrict__ lb_all,
-                                                       const double* __restrict__ ub_all, int max_eval, float znear,
-                                                       float zfar, double* __restrict__ x_out,
-                                                       double* __restrict__ f_out, int32_t* __restrict__ nev_out,
-                                                       float* __restrict__ part, uint32_t* __restrict__ bar,
-                                                       uint32_t* __restrict__ fail) {
-  constexpr int n = kNmDim;
-  constexpr int kT = kNmThreads / G;
-  __shared__ double pts[n + 1][n], vals[n + 1], lb[n], ub[n], xq[n], xr[n], cen[n];
-  __shared__ double fres;
-  __shared__ float sh[2 * kNmThreads / 64];
-  __shared__ int s_fail;
-  const int p = blockIdx.x / G, g = blockIdx.x % G, t = threadIdx.x;
-  const float* r = rec + (size_t)p * stride * 6;
-  const int nr = count[p];
-  int ne = 0;  // evaluations so far (the same in every thread of every workgroup of the problem)
-  if (t == 0) s_fail = 0;
-  auto eval = [&]() -> double {  // every thread; the point is xq (LDS)
-    __syncthreads();
-    float P[7];
-    for (int e = 0; e < n; e++) P[e] = (float)xq[e];  // the host path evaluates float32 points
-    float v;
-    if constexpr (G == 1) {
-      v = energy_rec(r, nr, P, znear, zfar, sh);
-    } else {
-      const int vt = g * kT + t;
-      const Quat q = rec_quat(P);
-      float s_, c_;
-      rec_sums(r, nr, q, P, znear, zfar, vt, s_, c_);
-      s_ = pcnn::wave_sum(s_);
-      c_ = pcnn::wave_sum(c_);
-      float* pp = part + ((size_t)p * 2 + (ne & 1)) * (2 * kNmThreads / 64);
-      if (pcnn::lane_id() == 0) {
-        pp[2 * (vt >> 6)] = s_;
-        pp[2 * (vt >> 6) + 1] = c_;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      __syncthreads();
-      if (t == 0 && !coop_arrive_wait(bar + p, (uint32_t)(ne + 1) * G, fail + p)) s_fail = 1;
-      __syncthreads();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      float S = 0.f, Cn = 0.f;
-      for (int w = 0; w < kNmThreads / 64; w++) {
-        S += pp[2 * w];
-        Cn += pp[2 * w + 1];
-      }
-      v = Cn > 0.f ? S / Cn : 0.f;  // distance /= c (:2520-2521)
-    }
-    ne++;
-    return (double)v;
-  };
-  auto clampq = [&](int e, double v) { return fmin(fmax(v, lb[e]), ub[e]); };  // np.minimum(np.maximum(p, lb), ub)
-  if (t == 0) {
-    for (int e = 0; e < n; e++) {
-      lb[e] = lb_all[(size_t)p * n + e];
-      ub[e] = ub_all[(size_t)p * n + e];
-      pts[0][e] = x0_all[(size_t)p * n + e];
-    }
-    for (int i = 0; i < n; i++) {
-      const double x0 = pts[0][i];
-      const double step = fmin(0.25 * (ub[i] - lb[i]), fmin(0.75 * (ub[i] - x0), 0.75 * (x0 - lb[i])));
-      for (int e = 0; e < n; e++) pts[i + 1][e] = pts[0][e] + (e == i ? step : 0.0);
-    }
-  }
-  for (int i = 0; i <= n && !s_fail; i++) {  // the initial simplex (one batch on the host: the same values)
-    if (t == 0)
-      for (int e = 0; e < n; e++) xq[e] = pts[i][e];
-    const double v = eval();
-    if (t == 0) vals[i] = v;
-  }
-  int nev = n + 1;
-  // nev and s_fail (read after each evaluation's barrier) are identical in
-  // every thread; a failed wait ends the search in every workgroup
-  while (nev < max_eval && !s_fail) {
-    if (t == 0) {
-      for (int i = 1; i <= n; i++) {  // stable insertion sort (np.argsort kind="stable")
-        for (int j = i; j > 0 && vals[j] < vals[j - 1]; j--) {
-          const double tv = vals[j];
-          vals[j] = vals[j - 1];
-          vals[j - 1] = tv;
-          for (int e = 0; e < n; e++) {
-            const double tp = pts[j][e];
-            pts[j][e] = pts[j - 1][e];
-            pts[j - 1][e] = tp;
-          }
-        }
-      }
-      for (int e = 0; e < n; e++) {  // np.mean(pts[:-1], axis=0): rows added in order, then / n
-        double s = pts[0][e];
-        for (int i = 1; i < n; i++) s = s + pts[i][e];
-        cen[e] = s / (double)n;
-      }
-      for (int e = 0; e < n; e++) {
-        xr[e] = clampq(e, cen[e] + (cen[e] - pts[n][e]));
-        xq[e] = xr[e];
-      }
-    }
-    const double fr = eval();
-    nev++;
-    __syncthreads();
-    const double v0 = vals[0], vn1 = vals[n - 1], vn = vals[n];
-    if (fr < v0 && nev < max_eval) {
-      if (t == 0)
-        for (int e = 0; e < n; e++) xq[e] = clampq(e, cen[e] + 2.0 * (cen[e] - pts[n][e]));
-      const double fe = eval();
-      nev++;
-      if (t == 0) {
-        const bool take_e = fe < fr;
-        for (int e = 0; e < n; e++) pts[n][e] = take_e ? xq[e] : xr[e];
-        vals[n] = take_e ? fe : fr;
-      }
-    } else if (fr < vn1) {
-      if (t == 0) {
-        for (int e = 0; e < n; e++) pts[n][e] = xr[e];
-        vals[n] = fr;
-      }
-    } else if (nev < max_eval) {
-      if (t == 0)
-        for (int e = 0; e < n; e++)
-          xq[e] = fr >= vn ? clampq(e, cen[e] + 0.5 * (pts[n][e] - cen[e])) : clampq(e, cen[e] + 0.5 * (xr[e] - cen[e]));
-      const double fc = eval();
-      nev++;
-      if (fc < fmin(fr, vn)) {
-        if (t == 0) {
-          for (int e = 0; e < n; e++) pts[n][e] = xq[e];
-          vals[n] = fc;
-        }
-      } else {
-        const int m = min(n, max_eval - nev);
-        for (int i = 1; i <= m && !s_fail; i++) {  // shrink toward the best (one batch on the host)
-          if (t == 0)
-            for (int e = 0; e < n; e++) xq[e] = clampq(e, pts[0][e] + 0.5 * (pts[i][e] - pts[0][e]));
-          const double fv = eval();
-          if (t == 0) {
-            for (int e = 0; e < n; e++) pts[i][e] = xq[e];
-            vals[i] = fv;
-          }
-        }
-        nev += m > 0 ? m : 0;
-      }
-    }
-    __syncthreads();
-  }
-  if (t == 0 && g == 0) {
-    int b = 0;
-    for (int i = 1; i <= n; i++)
-      if (vals[i] < vals[b]) b = i;  // np.argmin: the first minimum
-    for (int e = 0; e < n; e++) x_out[(size_t)p * n + e] = pts[b][e];
-    f_out[p] = vals[b];
-    nev_out[p] = nm_report(nev, s_fail, fail, p);
-  }
-  (void)fres;
-}
-
-// The same search with speculative rounds: kNmSpecW workgroup groups per
-// problem, each of G workgroups evaluating one point of a round.  A round
-// evaluates, in one arrive-and-wait, every point the next step may need:
-// reflection, expansion and both contractions of an iteration (the sequential
-// search then takes them in its own order and counts only those it uses), up
-// to kNmSpecW points of the initial simplex or of a shrink.  optEnergy is a
-// pure function of the point, so the simplex, the evaluation count and the
-// result are those of k_nm bit for bit; an iteration costs one round (plus
-// the shrink's) instead of one to three.
-constexpr int kNmSpecW = 4;
-template <int G, int S>
-__global__ void __launch_bounds__(kNmThreads / G) k_nm_spec(const float* __restrict__ rec,
-                                                            const int32_t* __restrict__ count, int stride,
-                                                            const double* __restrict__ x0_all,
-                                                            const double* __restrict__ lb_all,
-                                                            const double* __restrict__ ub_all, int max_eval,
-                                                            float znear, float zfar, double* __restrict__ x_out,
-                                                            double* __restrict__ f_out, int32_t* __restrict__ nev_out,
-                                                            float* __restrict__ part, uint32_t* __restrict__ bar,
-                                                            uint32_t* __restrict__ fail) {
-  constexpr int n = kNmDim;
-  constexpr int kT = kNmThreads / G;
-  constexpr int kW = 2 * kNmThreads / 64;  // (sum, count) per virtual wave
-  __shared__ double pts[n + 1][n], vals[n + 1], lb[n], ub[n], cen[n], xs[S][n], fs[S];
-  __shared__ int s_fail;
-  const int p = blockIdx.x / (G * S), sp = (blockIdx.x / G) % S, g = blockIdx.x % G, t = threadIdx.x;
-  const float* r = rec + (size_t)p * stride * 6;
-  const int nr = count[p];
-  int rnd = 0;  // rounds so far (the same in every thread of every workgroup of the problem)
-  if (t == 0) s_fail = 0;
-  auto round = [&](int cnt) {  // evaluate xs[0 .. cnt) -> fs[0 .. cnt), every thread
-    __syncthreads();
-    float* slot = part + ((size_t)p * 2 + (rnd & 1)) * S * kW;
-    if (sp < cnt) {
-      float P[7];
-      for (int e = 0; e < n; e++) P[e] = (float)xs[sp][e];  // the host path evaluates float32 points
-      const int vt = g * kT + t;
-      const Quat q = rec_quat(P);
-      float a, c;
-      rec_sums(r, nr, q, P, znear, zfar, vt, a, c);
-      a = pcnn::wave_sum(a);
-      c = pcnn::wave_sum(c);
-      if (pcnn::lane_id() == 0) {
-        slot[sp * kW + 2 * (vt >> 6)] = a;
-        slot[sp * kW + 2 * (vt >> 6) + 1] = c;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    if (t == 0 && !coop_arrive_wait(bar + p, (uint32_t)(rnd + 1) * G * S, fail + p)) s_fail = 1;
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (t < cnt) {  // value k: the 16 wave sums in order, as energy_rec
-      float S_ = 0.f, C_ = 0.f;
-      for (int w = 0; w < kNmThreads / 64; w++) {
-        S_ += slot[t * kW + 2 * w];
-        C_ += slot[t * kW + 2 * w + 1];
-      }
-      fs[t] = (double)(C_ > 0.f ? S_ / C_ : 0.f);  // distance /= c (:2520-2521)
-    }
-    rnd++;
-    __syncthreads();
-  };
-  auto clampq = [&](int e, double v) { return fmin(fmax(v, lb[e]), ub[e]); };
-  if (t == 0) {
-    for (int e = 0; e < n; e++) {
-      lb[e] = lb_all[(size_t)p * n + e];
-      ub[e] = ub_all[(size_t)p * n + e];
-      pts[0][e] = x0_all[(size_t)p * n + e];
-    }
-    for (int i = 0; i < n; i++) {
-      const double x0 = pts[0][i];
-      const double step = fmin(0.25 * (ub[i] - lb[i]), fmin(0.75 * (ub[i] - x0), 0.75 * (x0 - lb[i])));
-      for (int e = 0; e < n; e++) pts[i + 1][e] = pts[0][e] + (e == i ? step : 0.0);
-    }
-  }
-  for (int i0 = 0; i0 <= n && !s_fail; i0 += S) {  // the initial simplex
-    const int cnt = min(S, n + 1 - i0);
-    if (t == 0)
-      for (int k = 0; k < cnt; k++)
-        for (int e = 0; e < n; e++) xs[k][e] = pts[i0 + k][e];
-    round(cnt);
-    if (t == 0)
-      for (int k = 0; k < cnt; k++) vals[i0 + k] = fs[k];
-  }
-  int nev = n + 1;
-  while (nev < max_eval && !s_fail) {  // nev and s_fail are identical in every thread (a failed wait ends all)
-    __syncthreads();
-    if (t == 0) {
-      for (int i = 1; i <= n; i++) {  // stable insertion sort (np.argsort kind="stable")
-        for (int j = i; j > 0 && vals[j] < vals[j - 1]; j--) {
-          const double tv = vals[j];
-          vals[j] = vals[j - 1];
-          vals[j - 1] = tv;
-          for (int e = 0; e < n; e++) {
-            const double tp = pts[j][e];
-            pts[j][e] = pts[j - 1][e];
-            pts[j - 1][e] = tp;
-          }
-        }
-      }
-      for (int e = 0; e < n; e++) {  // np.mean(pts[:-1], axis=0): rows added in order, then / n
-        double sm = pts[0][e];
-        for (int i = 1; i < n; i++) sm = sm + pts[i][e];
-        cen[e] = sm / (double)n;
-      }
-      for (int e = 0; e < n; e++) {
-        const double xr = clampq(e, cen[e] + (cen[e] - pts[n][e]));
-        xs[0][e] = xr;                                            // reflection
-        xs[1][e] = clampq(e, cen[e] + 2.0 * (cen[e] - pts[n][e]));  // expansion
-        xs[2][e] = clampq(e, cen[e] + 0.5 * (xr - cen[e]));        // outside contraction
-        xs[3][e] = clampq(e, cen[e] + 0.5 * (pts[n][e] - cen[e]));  // inside contraction
-      }
-    }
-    round(4);
-    const double fr = fs[0];
-    nev++;
-    const double v0 = vals[0], vn1 = vals[n - 1], vn = vals[n];
-    __syncthreads();  // every thread holds v0 / vn1 / vn before thread 0 updates the simplex
-    if (fr < v0 && nev < max_eval) {
-      nev++;
-      if (t == 0) {
-        const bool take_e = fs[1] < fr;
-        for (int e = 0; e < n; e++) pts[n][e] = take_e ? xs[1][e] : xs[0][e];
-        vals[n] = take_e ? fs[1] : fr;
-      }
-    } else if (fr < vn1) {
-      if (t == 0) {
-        for (int e = 0; e < n; e++) pts[n][e] = xs[0][e];
-        vals[n] = fr;
-      }
-    } else if (nev < max_eval) {
-      nev++;
-      const int kc = fr >= vn ? 3 : 2;
-      const double fc = fs[kc];
-      if (fc < fmin(fr, vn)) {
-        if (t == 0) {
-          for (int e = 0; e < n; e++) pts[n][e] = xs[kc][e];
-          vals[n] = fc;
-        }
-      } else {
-        const int m = min(n, max_eval - nev);
-        for (int i0 = 1; i0 <= m && !s_fail; i0 += S) {  // shrink toward the best
-          const int cnt = min(S, m + 1 - i0);
-          __syncthreads();
-          if (t == 0)
-            for (int k = 0; k < cnt; k++)
-              for (int e = 0; e < n; e++) xs[k][e] = clampq(e, pts[0][e] + 0.5 * (pts[i0 + k][e] - pts[0][e]));
-          round(cnt);
-          if (t == 0)
-            for (int k = 0; k < cnt; k++) {
-              for (int e = 0; e < n; e++) pts[i0 + k][e] = xs[k][e];
-              vals[i0 + k] = fs[k];
-            }
-        }
-        nev += m > 0 ? m : 0;
-      }
-    }
-  }
-  __syncthreads();
-  if (t == 0 && g == 0 && sp == 0) {
-    int b = 0;
-    for (int i = 1; i <= n; i++)
-      if (vals[i] < vals[b]) b = i;  // np.argmin: the first minimum
-    for (int e = 0; e < n; e++) x_out[(size_t)p * n + e] = pts[b][e];
-    f_out[p] = vals[b];
-    nev_out[p] = nm_report(nev, s_fail, fail, p);
-  }
-}
-
-}  // namespace pcnn_refine
-
-extern "C" size_t pcnn_energy_records_workspace_size(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0) return 256;
-  const int nseg = (H * W + kSeg - 1) / kSeg;
-  return (size_t)N * nseg * sizeof(int32_t) + 256;
-}
-
-extern "C" int pcnn_energy_records(const float* live, int n_live, const int32_t* label, const float* pred_vertices,
-                                   int H, int W, float znear, float zfar, int N, const int32_t* prob_obj,
-                                   const int32_t* prob_live, float* records, int32_t* counts, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  PCNN_REQUIRE(live && label && pred_vertices && prob_obj && prob_live && records && counts && workspace);
-  PCNN_REQUIRE(N > 0 && H > 0 && W > 0 && n_live > 0 && (long)H * W < (1l << 30));
-  const int HW = H * W, nseg = (HW + kSeg - 1) / kSeg;
-  if (workspace_bytes < (size_t)N * nseg * sizeof(int32_t)) return PCNN_ECAPACITY;
-  int32_t* segcnt = (int32_t*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_rec_count, dim3(nseg, N), dim3(kBlk), 0, st, live, n_live, label, HW, znear, zfar, prob_obj,
-                     prob_live, nseg, segcnt);
-  hipLaunchKernelGGL(k_rec_scatter, dim3(nseg, N), dim3(kBlk), 0, st, live, n_live, label, pred_vertices, HW, znear,
-                     zfar, prob_obj, prob_live, nseg, segcnt, records, counts);
-  PCNN_CHECK_LAUNCH();
-  return PCNN_OK;
-}
-
-extern "C" int pcnn_energy_rec(const float* records, const int32_t* counts, int stride, const float* poses,
-                               const int32_t* pose_prob, int K, float znear, float zfar, float* energy, void* stream) {
-  PCNN_REQUIRE(records && counts && poses && pose_prob && energy && K > 0 && stride > 0);
-  hipLaunchKernelGGL(k_energy_rec, dim3(K), dim3(kNmThreads), 0, (hipStream_t)stream, records, counts, stride, poses,
-                     pose_prob, znear, zfar, energy);
-  PCNN_CHECK_LAUNCH();
-  return PCNN_OK;
-}
-
-extern "C" int pcnn_nelder_mead_energy(const float* records, const int32_t* counts, int stride, int N,
-                                       const double* x0, const double* lb, const double* ub, int max_eval,
-                                       float znear, float zfar, double* x_out, double* f_out, int32_t* nev_out,
-                                       void* stream) {
-  PCNN_REQUIRE(records && counts && x0 && lb && ub && x_out && f_out && nev_out && N > 0 && stride > 0);
-  // at least the initial simplex: NLopt's maxeval also counts it, and a
-  // budget below n + 1 is refused rather than overrun
-  PCNN_REQUIRE(max_eval >= pcnn_refine::kNmDim + 1 && max_eval <= (1 << 20));
-  hipLaunchKernelGGL(k_nm<1>, dim3(N), dim3(kNmThreads), 0, (hipStream_t)stream, records, counts, stride, x0, lb,
-                     ub, max_eval, znear, zfar, x_out, f_out, nev_out, nullptr, nullptr, nullptr);
-  PCNN_CHECK_LAUNCH();
-  return PCNN_OK;
-}
-
-// The same searches with kNmCoop workgroups per problem (the evaluation's
-// records spread over kNmCoop CUs), launched cooperatively so that the
-// workgroups of a problem are resident together; bit-identical results.
-constexpr int kNmCoop = 8;
-constexpr int kNmSpecMaxN = 32;  // N x 8 x 4 workgroups of 128 threads: 1024 at N = 32
-
-static inline size_t nm_part_bytes(int N) {  // per problem: 2 parities x kNmSpecW points x the wave sums
-  return pcnn::align_up((size_t)N * 2 * kNmSpecW * (2 * kNmThreads / 64) * sizeof(float), 256);
-}
-extern "C" size_t pcnn_nelder_mead_energy_workspace_size(int N) {
-  if (N <= 0) return 256;
-  return nm_part_bytes(N) + 2 * (size_t)N * sizeof(uint32_t) + 256;  // + the arrival counters and failure flags
-}
-
-extern "C" int pcnn_nelder_mead_energy_coop_path(const float* records, const int32_t* counts, int stride, int N,
-                                                 const double* x0, const double* lb, const double* ub, int max_eval,
-                                                 float znear, float zfar, double* x_out, double* f_out,
-                                                 int32_t* nev_out, void* workspace, size_t workspace_bytes,
-                                                 int force_path, int32_t* path_out, void* stream) {
-  PCNN_REQUIRE(records && counts && x0 && lb && ub && x_out && f_out && nev_out && N > 0 && stride > 0);
-  PCNN_REQUIRE(max_eval >= pcnn_refine::kNmDim + 1 && max_eval <= (1 << 20) && N <= 128);
-  PCNN_REQUIRE(force_path >= 0 && force_path <= 3);
-  if (!workspace || workspace_bytes < pcnn_nelder_mead_energy_workspace_size(N)) return PCNN_ECAPACITY;
-  float* part = (float*)workspace;
-  uint32_t* bar = (uint32_t*)((char*)workspace + nm_part_bytes(N));
-  uint32_t* fail = bar + N;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(bar, 0, 2 * (size_t)N * sizeof(uint32_t), st) != hipSuccess) return PCNN_EHIP;
-  void* args[] = {(void*)&records, (void*)&counts, (void*)&stride, (void*)&x0, (void*)&lb, (void*)&ub,
-                  (void*)&max_eval, (void*)&znear, (void*)&zfar, (void*)&x_out, (void*)&f_out, (void*)&nev_out,
-                  (void*)&part, (void*)&bar, (void*)&fail};
-  // speculative rounds while the N x kNmCoop x kNmSpecW workgroups fit the
-  // chip at once (path 1); then one evaluation per round (2); then one
-  // workgroup per problem (3).  force_path pins one (0: the first that
-  // launches); path_out (host int, may be null) reports the one that ran.
-  int path = 0;
-  if ((force_path == 0 || force_path == 1) && N <= kNmSpecMaxN &&
-      hipLaunchCooperativeKernel((const void*)k_nm_spec<kNmCoop, kNmSpecW>, dim3(N * kNmCoop * kNmSpecW),
-                                 dim3(kNmThreads / kNmCoop), args, 0, st) == hipSuccess)
-    path = 1;
-  if (!path) (void)hipGetLastError();
-  if (!path && (force_path == 0 || force_path == 2) &&
-      hipLaunchCooperativeKernel((const void*)k_nm<kNmCoop>, dim3(N * kNmCoop), dim3(kNmThreads / kNmCoop), args, 0,
-                                 st) == hipSuccess)
-    path = 2;
-  if (!path) (void)hipGetLastError();
-  if (!path && (force_path == 0 || force_path == 3)) {  // the one-workgroup search (same bits)
-    hipLaunchKernelGGL(k_nm<1>, dim3(N), dim3(kNmThreads), 0, st, records, counts, stride, x0, lb, ub, max_eval,
-                       znear, zfar, x_out, f_out, nev_out, nullptr, nullptr, nullptr);
-    path = 3;
-  }
-  if (path_out) *path_out = path;
-  if (!path) return PCNN_EHIP;  // the forced path could not launch
-  PCNN_CHECK_LAUNCH();
-  return PCNN_OK;
-}
-
-extern "C" int pcnn_nelder_mead_energy_coop(const float* records, const int32_t* counts, int stride, int N,
-                                            const double* x0, const double* lb, const double* ub, int max_eval,
-                                            float znear, float zfar, double* x_out, double* f_out, int32_t* nev_out,
-                                            void* workspace, size_t workspace_bytes, void* stream) {
-  return pcnn_nelder_mead_energy_coop_path(records, counts, stride, N, x0, lb, ub, max_eval, znear, zfar, x_out, f_out,
-                                           nev_out, workspace, workspace_bytes, 0, nullptr, stream);
 }

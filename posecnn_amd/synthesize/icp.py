@@ -1,5 +1,6 @@
 """Test-time pose refinement, backed by
-libposecnn_hip.so (csrc/icp.hip).
+libposecnn_hip.so (csrc/icp.hip; the record energy and the Nelder-Mead
+searches: csrc/pose_search.hip).
 
 Mirrors the numerical pieces of lib/synthesize (Synthesizer::solveICP,
 synthesize.cpp:2052-2395, exposed as synthesizer.icp_python,

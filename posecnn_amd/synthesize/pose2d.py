@@ -1,5 +1,5 @@
 """RGB-only pose estimation (the RANSAC half), backed
-by libposecnn_hip.so (csrc/pose2d.hip).
+by libposecnn_hip.so (csrc/pose2d.hip over csrc/pose_ransac.h).
 
 Mirrors Synthesizer.estimate_poses_2d (lib/synthesize/synthesizer.pyx:74-82)
 over Synthesizer::estimatePose2D (synthesize.cpp:1571-1766), as

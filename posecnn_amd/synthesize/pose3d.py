@@ -1,6 +1,6 @@
 """Depth-based pose estimation (the
 cfg.TEST.VERTEX_REG_3D branch), backed by libposecnn_hip.so
-(csrc/pose2d.hip, pcnn_pose3d).
+(csrc/pose3d.hip, pcnn_pose3d).
 
 Mirrors Synthesizer.estimate_poses_3d (lib/synthesize/synthesizer.pyx:86-95)
 over Synthesizer::estimatePose3D (synthesize.cpp:1769-1965), as

@@ -135,13 +135,22 @@ for rname, rnd in renderers.items():
             e2e[f"{key}_minus_renders_ms"] = round(e2e[f"{key}_ms"] - e2e[f"{key}_renders_ms"], 2)
 # the Nelder-Mead searches alone (pcnn_nelder_mead_energy: one workgroup per RoI, 50 evaluations)
 pv0 = render(sc["cls"], sc["init"])[1]
+r_ = np.array([0.1, 0.1, 0.1, 0.1, 0.01, 0.01, 0.1])
 for nroi in (1, 4):
     rec, cnt = R.energy_records(lv[:1].contiguous(), lab, [sc["cls"]] * nroi,
                                 [0] * nroi, pv0[None].expand(nroi, -1, -1, -1).contiguous())
     X0 = np.tile(np.array([[1, 0, 0, 0, 0, 0, 0]], np.float64), (nroi, 1))
-    r_ = np.array([0.1, 0.1, 0.1, 0.1, 0.01, 0.01, 0.1])
     e2e[f"nelder_mead_device_rois{nroi}_us"] = round(
         wall(lambda: R.nelder_mead_device(rec, cnt, X0, X0 - r_, X0 + r_, 50), reps=10) * 1e3, 1)
+# each launch path of the search (csrc/pose_search.hip): 4 problems forced to the speculative (1),
+# cooperative (2) and one-workgroup (3) kernels, then the sizes at which the default moves to 2 and 3
+for nroi, force in ((4, 1), (4, 2), (4, 3), (40, 0), (130, 0)):
+    rec, cnt = R.energy_records(lv[:1].contiguous(), lab, [sc["cls"]] * nroi,
+                                [0] * nroi, pv0[None].expand(nroi, -1, -1, -1).contiguous())
+    X0 = np.tile(np.array([[1, 0, 0, 0, 0, 0, 0]], np.float64), (nroi, 1))
+    key = f"nelder_mead_device_rois{nroi}_path{force}_us" if force else f"nelder_mead_device_rois{nroi}_auto_us"
+    e2e[key] = round(wall(lambda: R.nelder_mead_device(rec, cnt, X0, X0 - r_, X0 + r_, 50, force_path=force),
+                          reps=10) * 1e3, 1)
 res["solve_icp_end_to_end"] = {**e2e, "records_per_roi": int(cnt[0].item()),
                                "note": "wall time per solve_icp call (host orchestration, renders, all launches and "
                                        "host reads); rois share one frame; *_renders_ms = the caller's renders alone, "

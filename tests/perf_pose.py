@@ -1,7 +1,7 @@
 """Time the RANSAC pose estimators: estimatePose2D
 (--mode 2d, posecnn_amd.synthesize.pose2d) or estimatePose3D (--mode 3d,
-posecnn_amd.synthesize.pose3d; depth with 10 % holes and 1 mm noise), both in
-csrc/pose2d.hip, on a 640x480 ray-cast box scene (tests/pose2d_scene.py) with
+posecnn_amd.synthesize.pose3d; depth with 10 % holes and 1 mm noise), in
+csrc/pose2d.hip and csrc/pose3d.hip, on a 640x480 ray-cast box scene (tests/pose2d_scene.py) with
 device-resident inputs, and the oracle's single-thread restatement
 (oracle/orc_pose2d.cpp) on the same frame beside it as the CPU baseline (the
 reason this lives under tests/: only tests/, smoke() and bench.py's CPU leg

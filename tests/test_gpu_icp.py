@@ -1,4 +1,4 @@
-"""Pose refinement on the GPU (csrc/icp.hip through the C-ABI) against the
+"""Pose refinement on the GPU (csrc/icp.hip and csrc/pose_search.hip through the C-ABI) against the
 oracle restatement (oracle/orc_icp.cpp) of df::icp and solveICP's pieces
  on the synthetic box scene of refine_scene.py.
 
@@ -263,17 +263,31 @@ def test_solve_icp_batched_over_rois(hip):
         assert np.linalg.norm(picp[i, 4:] - trues[c][4:]) < 5e-3
 
 
-@pytest.mark.parametrize("max_eval", [8, 12, 50])
-def test_nelder_mead_device_matches_host(hip, orc, max_eval):
-    """refinePose's Nelder-Mead (poseWithOpt, synthesize.cpp:2529-2573) run
-    wholly on the device, one workgroup per problem (pcnn_nelder_mead_energy),
-    against the host search (icp.py nelder_mead) over the same record-based
-    optEnergy (pcnn_energy_rec): the same points, values and evaluation counts,
-    bit for bit, for max_eval equal to the initial simplex (8), with shrinks
-    (12) and at solveICP's 50 (budgets below the simplex are refused: NLopt's
-    maxeval counts it, test_nelder_mead_device_refuses_small_budget).  The record energy is optEnergy over the pixels of
-    the full-frame kernel (pcnn_pose_energy, parity-tested against the
-    oracle), summed in another fixed order."""
+_NM_HOST = {}
+
+
+def _nm_host_case(orc, max_eval):
+    """The three problems of test_nelder_mead_device_matches_host and their
+    host searches at one budget, computed once and shared by the launch paths
+    (nothing in it is modified afterwards)."""
+    from posecnn_amd.synthesize import icp as R
+    if "problems" not in _NM_HOST:
+        _NM_HOST["problems"] = _nm_problems(orc)
+    pb = _NM_HOST["problems"]
+    if max_eval not in _NM_HOST:
+        rec, cnt, x0, r = pb["rec"], pb["cnt"], pb["x0"], pb["r"]
+        host = []
+        for i in range(3):
+            def fn(p, i=i):
+                e = R.pose_energy_records(rec, cnt, torch.from_numpy(np.asarray(p, np.float32)[None]).to(D),
+                                          torch.tensor([i], dtype=torch.int32))
+                return float(e.cpu().numpy()[0])
+            host.append(R.nelder_mead(fn, x0[i], x0[i] - r, x0[i] + r, max_eval))
+        _NM_HOST[max_eval] = host
+    return pb, _NM_HOST[max_eval]
+
+
+def _nm_problems(orc):
     from posecnn_amd.synthesize import icp as R
     scs = [scene(s, perturb_deg=3.0, perturb_t=0.01) for s in (7, 8)]
     lvs = [_live(sc, orc)[0] for sc in scs]
@@ -290,14 +304,34 @@ def test_nelder_mead_device_matches_host(hip, orc, max_eval):
     x0 = np.array([[1, 0, 0, 0, 0, 0, 0], [1, 0, 0, 0, 0, 0, 0], [0.99, 0.02, -0.01, 0.0, 0.002, -0.001, 0.01]],
                   np.float64)
     r = np.array([0.1, 0.1, 0.1, 0.1, 0.01, 0.01, 0.1])
-    x, f, nev = R.nelder_mead_device(rec, cnt, x0, x0 - r, x0 + r, max_eval)
+    return dict(rec=rec, cnt=cnt, x0=x0, r=r, live=live, lab=lab, objs=objs, pv=pv)
+
+
+@pytest.mark.parametrize("max_eval", [8, 12, 50])
+@pytest.mark.parametrize("force_path", [1, 2, 3])
+def test_nelder_mead_device_matches_host(hip, orc, force_path, max_eval):
+    """refinePose's Nelder-Mead (poseWithOpt, synthesize.cpp:2529-2573) run
+    wholly on the device (pcnn_nelder_mead_energy_coop_path), on each of its
+    launch paths (1: speculative rounds, 2: cooperating workgroups, 3: one
+    workgroup per problem; all three hand their evaluator to the one search
+    of csrc/nelder_mead.h), against the host search (icp.py nelder_mead) over
+    the same record-based optEnergy (pcnn_energy_rec): the same points, values
+    and evaluation counts, bit for bit, for max_eval equal to the initial
+    simplex (8), with shrinks (12) and at solveICP's 50 (budgets below the
+    simplex are refused: NLopt's maxeval counts it,
+    test_nelder_mead_device_refuses_small_budget).  The record energy is
+    optEnergy over the pixels of the full-frame kernel (pcnn_pose_energy,
+    parity-tested against the oracle), summed in another fixed order."""
+    from posecnn_amd.synthesize import icp as R
+    pb, host = _nm_host_case(orc, max_eval)
+    rec, cnt, x0, r = pb["rec"], pb["cnt"], pb["x0"], pb["r"]
+    live, lab, objs, pv = pb["live"], pb["lab"], pb["objs"], pb["pv"]
+    x, f, nev, path = R.nelder_mead_device(rec, cnt, x0, x0 - r, x0 + r, max_eval, force_path=force_path,
+                                           return_path=True)
+    assert path == force_path
     x, f, nev = x.cpu().numpy(), f.cpu().numpy(), nev.cpu().numpy()
     for i in range(3):
-        def fn(p, i=i):
-            e = R.pose_energy_records(rec, cnt, torch.from_numpy(np.asarray(p, np.float32)[None]).to(D),
-                                      torch.tensor([i], dtype=torch.int32))
-            return float(e.cpu().numpy()[0])
-        hx, hf = R.nelder_mead(fn, x0[i], x0[i] - r, x0[i] + r, max_eval)
+        hx, hf = host[i]
         np.testing.assert_array_equal(x[i], hx)
         assert f[i] == hf
         assert nev[i] == max(8, max_eval)

@@ -1,4 +1,4 @@
-"""estimatePose2D on the GPU (csrc/pose2d.hip, posecnn_amd/synthesize/pose2d.py)
+"""estimatePose2D on the GPU (csrc/pose2d.hip over csrc/pose_ransac.h, posecnn_amd/synthesize/pose2d.py)
 against the restated reference (oracle/orc_pose2d.cpp) on ray-cast box scenes:
 the sampled hypotheses (object and pixel indices exact; poses to double
 rounding), every preemptive round's inlier counts and the survivors exact, the

@@ -1,4 +1,4 @@
-"""estimatePose3D on the GPU (csrc/pose2d.hip pcnn_pose3d,
+"""estimatePose3D on the GPU (csrc/pose3d.hip pcnn_pose3d,
 posecnn_amd/synthesize/pose3d.py) against the restated reference
 (oracle/orc_pose2d.cpp orc_pose3d) on ray-cast box scenes with depth: the
 camera coordinates, sampled hypotheses (objects, pixels, 3-point rigid

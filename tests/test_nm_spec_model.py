@@ -1,5 +1,6 @@
-"""CPU model of the device Nelder-Mead's speculative rounds (csrc/icp.hip
-k_nm_spec): every iteration evaluates the reflection, the expansion and both
+"""CPU model of the device Nelder-Mead's speculative rounds
+(csrc/pose_search.hip k_nm_spec: csrc/nelder_mead.h's search over a batching
+evaluator): every iteration evaluates the reflection, the expansion and both
 contractions in one round, the initial simplex and a shrink four points per
 round, and the search takes the values in the sequential order, counting only
 those it uses.  Because the objective is a pure function of the point, the
